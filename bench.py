@@ -7,8 +7,11 @@ candidates of a 64k tileset + tilemap items, all inputs resident in HBM before t
 Weak scaling: every rank tiles its own keyframe (keyframes are independent, main.pas:4005-4011);
 there is no data-path collective.  The tileset is broadcast once from rank 0 (RCCL) before timing.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` for the
-dominant kernel (nn_shortlist: MFMA) and a bounded `cpu_baseline` of the oracle on the same workload.
+Prints ONE JSON line on rank 0, with `roofline` for the dominant kernel (nn_shortlist: MFMA) from the timed
+steps' own HIP events.  A plain run does only that: set up, warm up, time the steps, write the last step's outputs
+(--dump-outputs DIR) and print the line.  --full adds what takes runs of its own: the bounded `cpu_baseline` of the
+oracle on the same workload (also the parity check) and the `secondary` lines (Prepare, Smooth, keyframe detection,
+Dither, palettes, GlobalTiling, per-tile calls, the sustained encoder loop).
 """
 from __future__ import annotations
 
@@ -49,6 +52,12 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="bounded CPU-baseline budget (rank 0)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = the host cores this process may use "
                     "(benchutil.host_cores: affinity mask, cgroup quota, the box's advertised share)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the CPU baseline / parity check and the secondary "
+                         "lines (each can still be switched off with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (rank 0's tilemap items and errors) "
+                         "as DIR/<name>.npy")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-smooth", action="store_true")
     ap.add_argument("--no-keyframes", action="store_true")
@@ -68,6 +77,9 @@ def main():
                     help="launcher self-test without a GPU: the ranks rendezvous over gloo, all-reduce their ranks "
                          "and rank 0 prints the world it saw (tests/test_bench_launch.py)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline only
+        args.no_cpu = args.no_smooth = args.no_keyframes = args.no_dither = args.no_globaltiling = True
+        args.no_palettes = args.no_encoder = args.no_per_call = True
 
     # --gpus N: one process per GPU.  Under an external launcher (torch.distributed.run) WORLD_SIZE must agree;
     # without one this process starts the N ranks itself BEFORE touching the GPU and relays rank 0's line.
@@ -200,6 +212,9 @@ def main():
     for t_ in (out_tile, out_pal, out_hm, out_vm, out_err):
         hh.update(t_.cpu().numpy().tobytes())
     out_digest = hh.hexdigest()[:16]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"tile": out_tile, "pal": out_pal, "hmirror": out_hm, "vmirror": out_vm,
+                                         "err": out_err})
     kernels = {}
     for name in ("psyv", "nn_prep", "nn_orbit", "nn_shortlist", "nn_rescore", "nn_pairs", "nn_collect", "nn_rescore2",
                  "nn_exact", "kd_verify", "kd_replay"):
@@ -278,7 +293,7 @@ def main():
 
     # ---- secondary: the keyframe's Prepare (reported separately from the FT step) ----
     prep = None
-    if rank == 0:
+    if rank == 0 and args.full:
         tps, kds = [], []
         for _ in range(3):  # steady state of an encoder walking keyframe after keyframe
             torch.cuda.synchronize(dev)
@@ -561,7 +576,7 @@ def main():
         res = {
             "metric": METRIC, "value": round(value, 4), "unit": "Mtiles/s", "n_gpus": world, "ranks_seen": ranks_seen,
             "process_group": dist.get_backend() if use_dist else None,
-            "steps": args.steps,
+            "steps": args.steps, "full": args.full,
             "warmup": args.warmup, "ms_per_step": round(ms_step, 3), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic (seeded, SURVEY.md 8(d))",
             "config": {"workload": f"{args.config.upper()}: {W}x{H} 8x8 tiles ({Q} tiles/frame), keyframe of {F} "
@@ -578,6 +593,24 @@ def main():
     kdt.close()
     if use_dist:
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path: str, outputs: dict) -> None:
+    """--dump-outputs: what the timed path left in the caller's buffers after its last step, one DIR/<name>.npy per
+    output array (float32; tile and palette indices are below 2^24, so exact).  Outputs that together would pass
+    DUMP_MAX_BYTES are cut to a fixed, seeded sample of their elements (the same elements of every array)."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: v.cpu().numpy().reshape(-1) for k, v in outputs.items()}
+    n = max(a.size for a in arrs.values())
+    keep = (DUMP_MAX_BYTES // len(arrs) - 1024) // 4  # 1024: room for each file's .npy header
+    sel = None
+    if n > keep:
+        sel = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), (a if sel is None else a[sel]).astype(np.float32))
 
 
 def rank_check() -> None:

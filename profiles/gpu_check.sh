@@ -12,7 +12,7 @@ timeout -k 10 400 python3 -u -m pytest tests -m gpu -x -v --timeout 120 --timeou
 echo "gpu tests done"
 timeout -k 10 200 python3 -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
 echo "smoke done"
-timeout -k 10 300 python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 300 python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 echo "bench done"
 if [ "${N2:-0}" = "1" ]; then
   # N>1 control flow rehearsed on the one-GPU box: 2 ranks on cuda:0 over gloo (the driver runs RCCL on 8 GPUs)

@@ -14,8 +14,8 @@ def main():
     import tiler_amd._lib as L
     L.LIB_PATH = os.path.abspath(sys.argv[1])
     tag = sys.argv[2]
-    sys.argv = ["bench.py", "--config", "c5", "--steps", "1", "--warmup", "1", "--no-cpu", "--no-smooth", "--no-keyframes",
-                "--no-dither", "--no-palettes", "--no-globaltiling", "--no-encoder"]
+    sys.argv = ["bench.py", "--full", "--config", "c5", "--steps", "1", "--warmup", "1", "--no-cpu", "--no-smooth",
+                "--no-keyframes", "--no-dither", "--no-palettes", "--no-globaltiling", "--no-encoder"]
     import bench
     buf = io.StringIO()
     with redirect_stdout(buf):

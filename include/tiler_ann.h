@@ -147,7 +147,7 @@ const char *tiler_last_error(void); /* thread-local message of the last failure 
 int tiler_set_gamma(double g0, double g1); /* gGamma main.pas:586 / 1441-1447; rebuilds gGammaCorLut */
 /* Kernel timing with HIP events on the launching stream (bench/profiling): enable, then read the
  * summed milliseconds and launch count of one kernel family ("psyv", "nn_prep", "nn_shortlist",
- * "nn_rescore", "nn_exact", "smooth", "kmodes").  Reading synchronises the recorded events. */
+ * "nn_rescore", "nn_exact", "smooth", "kmodes", "render", "quality").  Reading synchronises the recorded events. */
 int tiler_timing_enable(int on);
 double tiler_timing_get(const char *kernel, int *launches);
 int tiler_timing_reset(void);
@@ -259,6 +259,40 @@ int tiler_interframe_correlation_dev(const int32_t *d_rgb, int F, int tm_w, int 
 /* The shot-transition split (main.pas:1099-1132): kf_of_frame[F] = keyframe index of each frame.
  * tile_map_size = FTileMapSize.  Returns the keyframe count, or -1. */
 int tiler_find_keyframes(const double *corr, int F, int tile_map_size, int32_t *kf_of_frame);
+
+/* ---- Quality readout (Render main.pas:3305-3493, lblCorrel main.pas:3470-3489) ------------------------
+ * Render's destination frame from the tilemaps, as Render draws it with dithered, reduced and mirrored on and
+ * palIdx < 0.  Items are [F][Q] arrays (Q = tm_w * tm_h positions): tile/pal/hm/vm the TileMap, sm_* / smoothed the
+ * SmoothedTileMap (all five NULL: no Smooth was run); the item of a position is the smoothed one where
+ * smoothed != 0 (main.pas:3416-3418).  palpix[T][64], thm/tvm[T] the tileset; pixel (ty, tx) reads
+ * palpix[tile][tym*8+txm] with txm = 7-tx iff hm xor thm[tile], tym = 7-ty iff vm xor tvm[tile] (DrawTile
+ * main.pas:3318-3324) and takes colour palettes[pal_row0[f] + pal][index] out of palettes[n_rows][palsize]
+ * (0x00BBGGRR; pal_row0[F] = the row of palette 0 of the frame's keyframe, n_palettes per keyframe).
+ * out_rgb[F][Q][64] int32 0x00BBGGRR, tile-major (the layout FrameTiling and keyframe detection take frames in).
+ * Positions whose tile is outside [0, T) or whose pal is outside [0, n_palettes) (the reference skips them,
+ * main.pas:3422 / 3432, leaving the hatch brush) render 0 and are counted in invalid[F] (or NULL).  0 / -1. */
+int tiler_render_frames(int F, int Q, const int32_t *tile, const int32_t *pal, const uint8_t *hm, const uint8_t *vm,
+                        const int32_t *sm_tile, const int32_t *sm_pal, const uint8_t *sm_hm, const uint8_t *sm_vm,
+                        const uint8_t *smoothed, int T, const uint8_t *palpix, const uint8_t *thm, const uint8_t *tvm,
+                        int n_rows, int palsize, const int32_t *palettes, const int32_t *pal_row0, int n_palettes,
+                        int32_t *out_rgb, int32_t *invalid);
+/* Same with every array in HBM (out_rgb 16-byte, palpix 4-byte aligned); asynchronous on stream. */
+int tiler_render_frames_dev(int F, int Q, const int32_t *d_tile, const int32_t *d_pal, const uint8_t *d_hm,
+                            const uint8_t *d_vm, const int32_t *d_sm_tile, const int32_t *d_sm_pal,
+                            const uint8_t *d_sm_hm, const uint8_t *d_sm_vm, const uint8_t *d_smoothed, int T,
+                            const uint8_t *d_palpix, const uint8_t *d_thm, const uint8_t *d_tvm, int n_rows, int palsize,
+                            const int32_t *d_palettes, const int32_t *d_pal_row0, int n_palettes, int32_t *d_out_rgb,
+                            int32_t *d_invalid, void *stream);
+/* The figure under Render: corr[f] = ComputeCorrelationBGR(oriCorr, chgCorr) (main.pas:769-788) of source frame f
+ * against rendered frame f, both [tm_h*tm_w][64] tile-major, over the raster copy followed by the transposed copy
+ * (main.pas:3472-3486), bit-identical to the reference's sequential fp64 PearsonCorrelation (main.pas:1465-1492).
+ * sse[f][3]: the exact sum of squared byte differences of the R, G, B channels.  corr[F] and sse[F][3] are host
+ * arrays (either may be NULL).  0 / -1. */
+int tiler_frame_quality(const int32_t *src, const int32_t *dst, int F, int tm_w, int tm_h, double *corr,
+                        uint64_t *sse);
+/* Same with the frames in HBM (16-byte aligned); synchronous on stream. */
+int tiler_frame_quality_dev(const int32_t *d_src, const int32_t *d_dst, int F, int tm_w, int tm_h, double *corr,
+                            uint64_t *sse, void *stream);
 
 /* ---- Dither step, per tile (FinishDitherTiles main.pas:2482-2544) -------------------------
  * For n frame tiles rgb[n][64] (0x00BBGGRR) and their keyframe palette pal_of[n] (DitheringPalIndex) out of

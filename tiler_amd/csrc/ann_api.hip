@@ -29,6 +29,7 @@
 #include "nn_search.hpp"
 #include "orbit.hpp"
 #include "psyv.hpp"
+#include "quality.hpp"
 #include "smooth.hpp"
 
 namespace tiler {
@@ -1495,6 +1496,42 @@ int tiler_interframe_correlation_dev(const int32_t *d_rgb, int F, int tm_w, int 
 
 int tiler_find_keyframes(const double *corr, int F, int tile_map_size, int32_t *kf_of_frame) {
     return find_keyframes(corr, F, tile_map_size, kf_of_frame);
+}
+
+int tiler_render_frames(int F, int Q, const int32_t *tile, const int32_t *pal, const uint8_t *hm, const uint8_t *vm,
+                        const int32_t *sm_tile, const int32_t *sm_pal, const uint8_t *sm_hm, const uint8_t *sm_vm,
+                        const uint8_t *smoothed, int T, const uint8_t *palpix, const uint8_t *thm, const uint8_t *tvm,
+                        int n_rows, int palsize, const int32_t *palettes, const int32_t *pal_row0, int n_palettes,
+                        int32_t *out_rgb, int32_t *invalid) {
+    if (!ensure_init()) return -1;
+    return render_frames_host(F, Q, tile, pal, hm, vm, sm_tile, sm_pal, sm_hm, sm_vm, smoothed, T, palpix, thm, tvm,
+                              n_rows, palsize, palettes, pal_row0, n_palettes, out_rgb, invalid);
+}
+
+int tiler_render_frames_dev(int F, int Q, const int32_t *d_tile, const int32_t *d_pal, const uint8_t *d_hm,
+                            const uint8_t *d_vm, const int32_t *d_sm_tile, const int32_t *d_sm_pal,
+                            const uint8_t *d_sm_hm, const uint8_t *d_sm_vm, const uint8_t *d_smoothed, int T,
+                            const uint8_t *d_palpix, const uint8_t *d_thm, const uint8_t *d_tvm, int n_rows, int palsize,
+                            const int32_t *d_palettes, const int32_t *d_pal_row0, int n_palettes, int32_t *d_out_rgb,
+                            int32_t *d_invalid, void *stream) {
+    if (!ensure_init()) return -1;
+    DevScope ds(ptr_device(d_out_rgb));
+    return render_frames_dev(F, Q, d_tile, d_pal, d_hm, d_vm, d_sm_tile, d_sm_pal, d_sm_hm, d_sm_vm, d_smoothed, T,
+                             d_palpix, d_thm, d_tvm, n_rows, palsize, d_palettes, d_pal_row0, n_palettes, d_out_rgb,
+                             d_invalid, (hipStream_t)stream);
+}
+
+int tiler_frame_quality(const int32_t *src, const int32_t *dst, int F, int tm_w, int tm_h, double *corr,
+                        uint64_t *sse) {
+    if (!ensure_init()) return -1;
+    return frame_quality_host(src, dst, F, tm_w, tm_h, corr, sse);
+}
+
+int tiler_frame_quality_dev(const int32_t *d_src, const int32_t *d_dst, int F, int tm_w, int tm_h, double *corr,
+                            uint64_t *sse, void *stream) {
+    if (!ensure_init()) return -1;
+    DevScope ds(ptr_device(d_src));
+    return frame_quality_dev(d_src, d_dst, F, tm_w, tm_h, corr, sse, (hipStream_t)stream);
 }
 
 int tiler_kmodes_medoids(const uint8_t *X, int n, const int32_t *labels, const uint8_t *centroids, int k,

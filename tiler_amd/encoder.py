@@ -208,6 +208,46 @@ class Encoder:
         return gtm.assemble_stream([comps[k] for k in range(self.kf_start.size - 1)], self.kf_start, width, height,
                                    fps)
 
+    def render(self, on_screen: bool = False):
+        """The held frames rebuilt from the tilemaps on the GPU (DrawTile main.pas:3308-3343), each frame with its
+        keyframe's palettes: from the SmoothedTileMaps if do_smooth has run -- the items SaveStream writes, so the
+        picture a GTM player shows -- else from the TileMaps.  on_screen = True gives what Render draws instead
+        (main.pas:3416-3418: the SmoothedTileMap item only where Smoothed is set, the TileMap item elsewhere); the
+        two differ where DoTemporalSmoothing rewrote a previous frame's item and left its flag clear (main.pas:4110).
+        Returns (rgb [frames][Q][64] int32 0x00BBGGRR, invalid [frames])."""
+        from .quality import render_frames
+        P = self.n_palettes
+        row0 = np.zeros(self.frames, np.int32)
+        for k in self.kfs:
+            row0[self.rows(k)] = k * P
+        tail = (self.palpix, self.thm, self.tvm, self.palettes.reshape(-1, self.palettes.shape[-1]), row0, P)
+        sm = self.sm
+        if sm is None:
+            return render_frames(self.tile, self.pal, self.hm, self.vm, *tail)
+        if on_screen:
+            return render_frames(self.tile, self.pal, self.hm, self.vm, *tail, sm["tile"], sm["pal"], sm["hm"],
+                                 sm["vm"], sm["smoothed"])
+        return render_frames(sm["tile"], sm["pal"], sm["hm"], sm["vm"], *tail)
+
+    def quality(self, frames=None, *, width: int, height: int) -> dict:
+        """The figure Render shows (lblCorrel main.pas:3488) for every held frame: the frames of render() (the
+        SmoothedTileMaps if Smooth has run, i.e. the encode as it is written, else the TileMaps) scored against
+        `frames` ([held frames][Q][64], default: the source frames given to the constructor).  width / height in
+        pixels as for save_stream (the Video carries only Q, and the figure's transposed half depends on the
+        shape).  Returns per-frame corr (bit-identical to ComputeCorrelationBGR), psnr, sse [.][3], and the
+        rendered frames (rgb, invalid).  A DistributedEncoder returns its own frames' values (rows as `frame_idx`)."""
+        from .quality import frame_quality, psnr
+        Q = self.tiles_per_frame
+        tm_w, tm_h = int(width) // 8, int(height) // 8
+        if tm_w <= 0 or tm_h <= 0 or tm_w * tm_h != Q:
+            raise ValueError("quality: width x height does not match the tilemap size")
+        src = np.asarray(self.frame_rgb if frames is None else frames)
+        if src.size != self.frames * Q * 64:
+            raise ValueError("quality: frames must be the held frames, [frames][Q][64]")
+        rgb, invalid = self.render()
+        corr, sse = frame_quality(src, rgb, tm_w, tm_h)
+        return {"corr": corr, "psnr": psnr(sse, tm_w, tm_h), "sse": sse, "rgb": rgb, "invalid": invalid}
+
     def run_all(self, desired: int, quality: int = ft.FT_MEDIUM, strength: float = DEFAULT_STRENGTH):
         """btnRunAllClick main.pas:1232-1272 from MakeUnique to Smooth."""
         self.do_make_unique()

@@ -92,7 +92,16 @@ typedef struct {
     int64_t flat_queries;     /* queries of the last FrameTiling call in shortlist workgroups made of flat tiles only
                                  (flat tiles are grouped last; such a workgroup runs isotypic block 0 only: 3 k-steps
                                  per candidate block instead of orbit_ksteps / blocks).  Flat tiles that share a
-                                 workgroup with non-flat ones are not counted.  0 for searches without flat grouping. */
+                                 workgroup with non-flat ones are not counted.  0 for searches without flat grouping.
+                                 Always in the units of the call's own tiles: when the call searched its distinct
+                                 tiles only (dup_queries > 0) this is queries - ceil(n / W) * W for the call's n
+                                 non-flat tiles, duplicates included, and W queries per workgroup -- the layout the
+                                 call would have had without dedupe; searched_flat_queries is what ran. */
+    int64_t searched_queries; /* queries the last search ran: `queries`, or the distinct tiles of a FrameTiling call of
+                                 >= 8,192 tiles in which at least one tile in eight repeats another of the same call
+                                 (each distinct tile is searched once and its result copied to its repeats) */
+    int64_t searched_flat_queries; /* searched queries in shortlist workgroups made of flat tiles only */
+    int64_t dup_queries;      /* queries - searched_queries (0 when the call was searched tile by tile) */
 } tiler_search_stats;
 int ann_kdtree_get_stats(ann_kdtree *akd, tiler_search_stats *out);
 /* Search batches of at most max_k1 queries (k = 1; default 64) or max_k8 (k <= 8; default 16) -- the coalesced
@@ -106,6 +115,12 @@ int tiler_debug_force_replay(int on);
  * best key so far bounds what its lists may need), for A/B timing; answers are identical either
  * way.  Default 1.  0. */
 int tiler_debug_shortlist_gate(int on);
+/* Test / bench hook (process-wide): how a FrameTiling call of >= 8,192 tiles treats tiles that repeat inside the call.
+ * 1 (default): every distinct tile is searched once (exact: a hash table groups the tiles, all 64 words are compared
+ * before two tiles share a result); 0: every tile is searched, for A/B timing; 2: as 1 with the hash cut to 4 bits, so
+ * nearly every lookup meets a different tile and the word comparison carries the load.  Answers are identical in all
+ * three.  0, or -1 for another mode. */
+int tiler_debug_ft_dedup(int mode);
 /* Coalescing counters of the single-query entry points on this handle: calls, batches searched, largest batch. */
 int tiler_combine_stats(ann_kdtree *akd, int64_t *calls, int64_t *batches, int32_t *max_batch);
 /* Test / bench hook: the reference's per-call pattern timed natively (no interpreter between the calls): the first
@@ -147,7 +162,8 @@ const char *tiler_last_error(void); /* thread-local message of the last failure 
 int tiler_set_gamma(double g0, double g1); /* gGamma main.pas:586 / 1441-1447; rebuilds gGammaCorLut */
 /* Kernel timing with HIP events on the launching stream (bench/profiling): enable, then read the
  * summed milliseconds and launch count of one kernel family ("psyv", "nn_prep", "nn_shortlist",
- * "nn_rescore", "nn_exact", "smooth", "kmodes", "render", "quality").  Reading synchronises the recorded events. */
+ * "nn_rescore", "nn_exact", "smooth", "kmodes", "render", "quality", "ft_dedup": FrameTiling's duplicate-tile
+ * passes and scatter).  Reading synchronises the recorded events. */
 int tiler_timing_enable(int on);
 double tiler_timing_get(const char *kernel, int *launches);
 int tiler_timing_reset(void);

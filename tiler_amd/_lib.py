@@ -35,7 +35,9 @@ class SearchStats(ctypes.Structure):
                 ("orbit_groups", ctypes.c_int64), ("orbit_search", ctypes.c_int32), ("orbit_ksteps", ctypes.c_int32),
                 ("orbit_expansions", ctypes.c_int64), ("orbit_rescored", ctypes.c_int64),
                 ("tie_order", ctypes.c_int32), ("kd_levels", ctypes.c_int32), ("kd_build_ms", ctypes.c_double),
-                ("kd_replayed", ctypes.c_int64), ("flat_queries", ctypes.c_int64)]
+                ("kd_replayed", ctypes.c_int64), ("flat_queries", ctypes.c_int64),
+                ("searched_queries", ctypes.c_int64), ("searched_flat_queries", ctypes.c_int64),
+                ("dup_queries", ctypes.c_int64)]
 
 
 class PrepareInfo(ctypes.Structure):
@@ -61,6 +63,7 @@ _SIGS = {
                                           P(c_double)]),
     "tiler_debug_force_replay": (c_int, [c_int]),
     "tiler_debug_shortlist_gate": (c_int, [c_int]),
+    "tiler_debug_ft_dedup": (c_int, [c_int]),
     "tiler_combine_stats": (c_int, [c_void_p, P(ctypes.c_int64), P(ctypes.c_int64), P(ctypes.c_int32)]),
     "tiler_init": (c_int, [c_int]),
     "tiler_device_count": (c_int, []),

@@ -135,7 +135,9 @@ class KDTree:
                 "orbit_groups": s.orbit_groups, "orbit_search": s.orbit_search, "orbit_ksteps": s.orbit_ksteps,
                 "orbit_expansions": s.orbit_expansions, "orbit_rescored": s.orbit_rescored,
                 "tie_order": s.tie_order, "kd_levels": s.kd_levels, "kd_build_ms": round(s.kd_build_ms, 3),
-                "kd_replayed": s.kd_replayed, "flat_queries": s.flat_queries}
+                "kd_replayed": s.kd_replayed, "flat_queries": s.flat_queries,
+                "searched_queries": s.searched_queries, "searched_flat_queries": s.searched_flat_queries,
+                "dup_queries": s.dup_queries}
 
     def combine_stats(self) -> dict:
         """Coalescing of concurrent single-query calls on this handle (tiler_combine_stats)."""

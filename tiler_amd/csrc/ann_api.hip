@@ -1009,6 +1009,15 @@ int tiler_debug_shortlist_gate(int on) {
     return 0;
 }
 
+int tiler_debug_ft_dedup(int mode) {
+    if (mode < 0 || mode > 2) {
+        set_error("tiler_debug_ft_dedup: mode must be 0, 1 or 2");
+        return -1;
+    }
+    nn_set_ft_dedup(mode);
+    return 0;
+}
+
 int tiler_combine_stats(ann_kdtree *t, int64_t *calls, int64_t *batches, int32_t *max_batch) {
     if (!t) {
         set_error("tiler_combine_stats: null handle");
@@ -1111,11 +1120,20 @@ int ann_kdtree_get_stats(ann_kdtree *t, tiler_search_stats *out) {
     out->kd_build_ms = t->ix->kd ? t->ix->kd->build_ms : 0.0;
     out->kd_replayed = 0;
     out->flat_queries = 0;
+    out->searched_queries = t->ix->last_searched;
+    out->searched_flat_queries = 0;
+    out->dup_queries = t->ix->last_dup;
     if (const NNIndex *ix = t->ix; ix->last_flat_dev) {  // queries in all-flat shortlist workgroups
         int others = 0;
         TILER_HIP_CHECK(hipMemcpy(&others, ix->last_flat_dev, sizeof(int), hipMemcpyDeviceToHost));
         const long wf0 = std::min(ix->last_flat_wgs, (others + ix->last_flat_qpw - 1) / ix->last_flat_qpw);
-        out->flat_queries = wf0 < ix->last_flat_wgs ? ix->last_flat_nq - wf0 * ix->last_flat_qpw : 0;
+        out->searched_flat_queries = wf0 < ix->last_flat_wgs ? ix->last_flat_nq - wf0 * ix->last_flat_qpw : 0;
+        out->flat_queries = out->searched_flat_queries;
+        if (ix->last_ft_nonflat >= 0) {  // distinct tiles searched: the same layout over the call's own tiles
+            const long qpw = ix->last_flat_qpw, Q = (long)ix->last_queries;
+            const long wgs = (Q + qpw - 1) / qpw, w0 = std::min(wgs, ((long)ix->last_ft_nonflat + qpw - 1) / qpw);
+            out->flat_queries = w0 < wgs ? Q - w0 * qpw : 0;
+        }
     }
     if (t->ix->kd && t->ix->scratch.kd_count) {
         int c = 0;

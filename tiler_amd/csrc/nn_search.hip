@@ -1697,6 +1697,11 @@ void nn_scratch_free(SearchScratch &s, bool synced) {
     dfree(s.fpal);
     dfree(s.fhm);
     dfree(s.fvm);
+    dfree(s.dkey);
+    dfree(s.dmin);
+    dfree(s.dslot);
+    dfree(s.drep);
+    dfree(s.dpos);
     s = SearchScratch();
 }
 
@@ -1717,6 +1722,7 @@ void nn_index_destroy(NNIndex *ix) {
     dfree(ix->d_tr_attr);
     nn_scratch_free(ix->scratch, true);
     pinned_slot_free(ix->h_fb_count);
+    pinned_slot_free(ix->h_ft_cnt);
     if (ix->done_event) hipEventDestroy(ix->done_event);
     delete ix;
 }
@@ -1980,6 +1986,9 @@ int nn_search_dev(NNIndex *ix, const float *d_q, int nq, int k, int *d_idx, floa
         ra.m_vm = maps->vm;
     }
     ix->last_queries = nq;
+    ix->last_searched = nq;
+    ix->last_dup = 0;
+    ix->last_ft_nonflat = -1;
     ix->last_flat_dev = nullptr;
     SearchScratch &s = ix->scratch;
     if (!ix->done_event) TILER_HIP_CHECK(hipEventCreateWithFlags(&ix->done_event, hipEventDisableTiming));
@@ -2287,9 +2296,12 @@ __global__ __launch_bounds__(256) void ft_flat_flag_kernel(const int32_t *__rest
     if (threadIdx.x == 0) bcnt[blockIdx.x] = c;
 }
 
+// (one workgroup per row of counts: bcnt [gridDim.x][nb], total [gridDim.x])
 __global__ __launch_bounds__(1024) void ft_flat_scan_kernel(int *bcnt, int nb, int *total) {
     __shared__ int sc[1024];
     __shared__ int carry;
+    bcnt += (size_t)blockIdx.x * nb;
+    total += blockIdx.x;
     if (threadIdx.x == 0) carry = 0;
     __syncthreads();
     for (int b0 = 0; b0 < nb; b0 += 1024) {
@@ -2349,6 +2361,162 @@ __global__ __launch_bounds__(256) void ft_unpermute_kernel(int Q, const int *__r
     if (maps.vm) maps.vm[o] = fvm[p];
 }
 
+// Each distinct tile of a call is searched once.  A tile's answer is a function of its 64 RGB words and the handle, and
+// a keyframe batch is consecutive frames of one shot, so most tiles repeat the tile at their position one frame
+// earlier.  Nothing outlives the call: the table is cleared, filled, verified and scattered from in every call.
+//   A (ft_dedup_hash_kernel): per tile the flat flag and a 64-bit hash of its words; the key claims a slot of the
+//      open-addressing table (64-bit CAS) and the slot keeps the smallest tile index of its key (atomicMin).  Which
+//      slot a key gets depends on the race, what a lookup returns does not.
+//   B (ft_dedup_rep_kernel): tile i reads its key's first index r; r == i: a representative; else all 64 words are
+//      compared with tile r's: equal -> rep_of[i] = r (r is a representative: no chains), different (a hash collision)
+//      -> i represents itself, so the method is exact whatever the hash does.  Per-block counts of the non-flat and
+//      the flat representatives and of the call's non-flat tiles.
+//   ft_flat_scan_kernel over the three rows of counts, then C (ft_dedup_place_kernel): stable positions of the
+//      representatives, non-flat first, flat after, each in tile order (no atomics: the layout is deterministic).
+//   D (ft_dedup_scatter_kernel): every tile takes the outputs at its representative's position.
+// 16 lanes per tile (one int4 each: a wave reads 1 KiB contiguous), 16 tiles per group, 256 tiles per workgroup.
+static constexpr unsigned long long FT_DD_EMPTY = ~0ull;
+
+__device__ __forceinline__ unsigned long long ft_dd_mix(unsigned long long x) {  // splitmix64's finaliser
+    x ^= x >> 30;
+    x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27;
+    x *= 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    return x;
+}
+
+// the 16 ballot bits of this lane's group of 16
+__device__ __forceinline__ unsigned ft_dd_group_bits(unsigned long long b) {
+    return (unsigned)(b >> (threadIdx.x & 48)) & 0xffffu;
+}
+
+__global__ __launch_bounds__(256) void ft_dedup_hash_kernel(const int32_t *__restrict__ rgb, int Q,
+                                                            unsigned long long kmask, unsigned long long *tkey,
+                                                            unsigned int *tmin, unsigned int tmask, uint8_t *flag,
+                                                            int *slot) {
+    const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
+    const long base = (long)blockIdx.x * 256;
+    for (int it = 0; it < 16; it++) {
+        const long i = base + it * 16 + g;  // uniform over the group of 16
+        const bool in = i < Q;
+        int4 v = make_int4(0, 0, 0, 0);
+        if (in) v = reinterpret_cast<const int4 *>(rgb)[i * 16 + l];
+        const int c0 = __shfl(v.x, 0, 16);
+        const bool flat = ft_dd_group_bits(__ballot(v.x == c0 && v.y == c0 && v.z == c0 && v.w == c0)) == 0xffffu;
+        const unsigned long long a = ((unsigned long long)(unsigned)v.x << 32) | (unsigned)v.y;
+        const unsigned long long b = ((unsigned long long)(unsigned)v.z << 32) | (unsigned)v.w;
+        // position-salted terms, summed over the 16 lanes
+        unsigned long long h = ft_dd_mix(a + 0x9E3779B97F4A7C15ull * (unsigned)(2 * l + 1)) +
+                               ft_dd_mix(b + 0x9E3779B97F4A7C15ull * (unsigned)(2 * l + 2));
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) h += __shfl_xor(h, o, 16);
+        if (l != 0 || !in) continue;
+        unsigned long long key = ft_dd_mix(h) & kmask;
+        if (key == FT_DD_EMPTY) key = 0;
+        unsigned int s = (unsigned int)(key ^ (key >> 32)) & tmask;
+        for (;;) {  // at most Q keys in >= 2 Q slots: an empty slot or the key's own is always met
+            unsigned long long cur = __atomic_load_n(&tkey[s], __ATOMIC_RELAXED);  // (a stale EMPTY is settled by the CAS; a key never changes once set)
+            if (cur == FT_DD_EMPTY) {
+                cur = atomicCAS(&tkey[s], FT_DD_EMPTY, key);
+                if (cur == FT_DD_EMPTY) cur = key;
+            }
+            if (cur == key) break;
+            s = (s + 1) & tmask;
+        }
+        atomicMin(&tmin[s], (unsigned int)i);
+        slot[i] = (int)s;
+        flag[i] = flat ? 1 : 0;
+    }
+}
+
+__global__ __launch_bounds__(256) void ft_dedup_rep_kernel(const int32_t *__restrict__ rgb, int Q,
+                                                           const unsigned int *__restrict__ tmin,
+                                                           const int *__restrict__ slot,
+                                                           const uint8_t *__restrict__ flag, int *rep_of, int *bcnt,
+                                                           int nb) {
+    __shared__ int cnt[3];
+    if (threadIdx.x < 3) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
+    const long base = (long)blockIdx.x * 256;
+    int c_nf = 0, c_fl = 0, c_all = 0;
+    for (int it = 0; it < 16; it++) {
+        const long i = base + it * 16 + g;
+        const bool in = i < Q;
+        const long r = in ? (long)tmin[slot[i]] : 0;  // <= i: tile i itself took part in the minimum
+        const bool cmp = in && r != i;
+        bool eq = true;
+        if (cmp) {
+            const int4 a = reinterpret_cast<const int4 *>(rgb)[i * 16 + l];
+            const int4 b = reinterpret_cast<const int4 *>(rgb)[r * 16 + l];
+            eq = a.x == b.x && a.y == b.y && a.z == b.z && a.w == b.w;
+        }
+        const bool same = ft_dd_group_bits(__ballot(eq)) == 0xffffu;
+        if (l != 0 || !in) continue;
+        const bool dup = cmp && same;
+        rep_of[i] = dup ? (int)r : (int)i;
+        const int f = flag[i];
+        c_all += f ? 0 : 1;
+        if (!dup) {
+            c_nf += f ? 0 : 1;
+            c_fl += f ? 1 : 0;
+        }
+    }
+    if (l == 0) {
+        atomicAdd(&cnt[0], c_nf);
+        atomicAdd(&cnt[1], c_fl);
+        atomicAdd(&cnt[2], c_all);
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) bcnt[(size_t)threadIdx.x * nb + blockIdx.x] = cnt[threadIdx.x];
+}
+
+// boff: the scanned counts [3][nb]; total [0]: non-flat representatives
+__global__ __launch_bounds__(256) void ft_dedup_place_kernel(int Q, const uint8_t *__restrict__ flag,
+                                                             const int *__restrict__ rep_of,
+                                                             const int *__restrict__ boff, int nb,
+                                                             const int *__restrict__ total, int *perm, int *slot_of) {
+    __shared__ int sc[256];
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const bool rep = i < Q && rep_of[i] == (int)i;
+    const int f = rep ? flag[i] : 0;
+    const int mine = rep ? (f ? 1 << 16 : 1) : 0;  // low half: non-flat representatives, high half: flat ones
+    sc[threadIdx.x] = mine;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {
+        const int u = threadIdx.x >= o ? sc[threadIdx.x - o] : 0;
+        __syncthreads();
+        sc[threadIdx.x] += u;
+        __syncthreads();
+    }
+    if (!rep) return;
+    const int before = sc[threadIdx.x] - mine;
+    const long pos = f ? (long)*total + boff[(size_t)nb + blockIdx.x] + (before >> 16)
+                       : (long)boff[blockIdx.x] + (before & 0xffff);
+    perm[pos] = (int)i;
+    slot_of[i] = (int)pos;
+}
+
+__global__ __launch_bounds__(256) void ft_dedup_scatter_kernel(int Q, const int *__restrict__ rep_of,
+                                                               const int *__restrict__ slot_of, const int *fidx,
+                                                               const float *ferr, const int32_t *ftile,
+                                                               const int32_t *fpal, const uint8_t *fhm,
+                                                               const uint8_t *fvm, int *idx, float *err, FtMaps maps) {
+    const long o = (long)blockIdx.x * 256 + threadIdx.x;
+    if (o >= Q) return;
+    const long p = slot_of[rep_of[o]];
+    if (idx) idx[o] = fidx[p];
+    if (err) err[o] = ferr[p];
+    if (maps.tile) maps.tile[o] = ftile[p];
+    if (maps.pal) maps.pal[o] = fpal[p];
+    if (maps.hm) maps.hm[o] = fhm[p];
+    if (maps.vm) maps.vm[o] = fvm[p];
+}
+
+static std::atomic<int> g_ft_dedup{1};  // tiler_debug_ft_dedup
+void nn_set_ft_dedup(int mode) { g_ft_dedup.store(mode); }
+
 int nn_frame_tiling_dev(NNIndex *ix, const int32_t *d_rgb, int Q, int use_wavelets, int gamma, int *d_idx,
                         float *d_err, const FtMaps *maps, hipStream_t stream) {
     if (Q <= 0) return 0;
@@ -2371,53 +2539,124 @@ int nn_frame_tiling_dev(NNIndex *ix, const int32_t *d_rgb, int Q, int use_wavele
     // flat grouping on the generic path (datasets without mirror orbits: real PrepareFrameTiling candidate sets):
     // the 16x16x32 shortlist's flat workgroups contract k-step 0 only (dc_first_dim)
     const bool flat_generic = !ix->orbit && use_wavelets && ix->S16 > 0 && shortlist16_L() > 0 && Q >= 8192;
-    if (flat_generic || (ix->orbit && use_wavelets)) {
-        // flat tiles last (see ft_flat_flag_kernel) when the shortlist is long enough to repay the ~0.1 ms of
-        // grouping: C3 (2,048 group blocks) -0.6..-1.1 ms per step; C2 (512 blocks, whose ragged last round the mixed
-        // split already fills) +0.08 ms (profiles/flat_c2_ab.sh), so not there
-        if (!noflat && Q >= 8192 && (flat_generic || ((const OrbitIndex *)ix->orbit)->gblk >= 1024)) {
-            const int nb = (Q + 255) / 256;
-            if ((size_t)Q > s.cap_flat) {
-                if (s.fperm || s.fbcnt || s.fflag || s.fidx || s.ferr || s.ftile || s.fpal || s.fhm || s.fvm)
-                    (void)hipDeviceSynchronize();  // (as above)
-                dfree(s.fperm);
-                dfree(s.fbcnt);
-                dfree(s.fflag);
-                dfree(s.fidx);
-                dfree(s.ferr);
-                dfree(s.ftile);
-                dfree(s.fpal);
-                dfree(s.fhm);
-                dfree(s.fvm);
-                s.fperm = s.fbcnt = s.fidx = nullptr;  // a failed allocation below leaves nothing dangling
-                s.fflag = s.fhm = s.fvm = nullptr;
-                s.ferr = nullptr;
-                s.ftile = s.fpal = nullptr;
-                s.cap_flat = 0;
-                if (!s.fcnt) TILER_HIP_CHECK(dmalloc((void **)&s.fcnt, sizeof(int)));
-                TILER_HIP_CHECK(dmalloc((void **)&s.fperm, (size_t)Q * sizeof(int)));
-                TILER_HIP_CHECK(dmalloc((void **)&s.fbcnt, (size_t)nb * sizeof(int)));
-                TILER_HIP_CHECK(dmalloc((void **)&s.fflag, (size_t)Q));
-                TILER_HIP_CHECK(dmalloc((void **)&s.fidx, (size_t)Q * sizeof(int)));
-                TILER_HIP_CHECK(dmalloc((void **)&s.ferr, (size_t)Q * sizeof(float)));
-                TILER_HIP_CHECK(dmalloc((void **)&s.ftile, (size_t)Q * sizeof(int32_t)));
-                TILER_HIP_CHECK(dmalloc((void **)&s.fpal, (size_t)Q * sizeof(int32_t)));
-                TILER_HIP_CHECK(dmalloc((void **)&s.fhm, (size_t)Q));
-                TILER_HIP_CHECK(dmalloc((void **)&s.fvm, (size_t)Q));
-                s.cap_flat = Q;
+    // flat tiles last (see ft_flat_flag_kernel) when the shortlist is long enough to repay the ~0.1 ms of grouping: C3
+    // (2,048 group blocks) -0.6..-1.1 ms per step; C2 (512 blocks, whose ragged last round the mixed split already
+    // fills) +0.08 ms (profiles/flat_c2_ab.sh), so not there
+    const bool group = !noflat && Q >= 8192 &&
+                       (flat_generic || (ix->orbit && use_wavelets && ((const OrbitIndex *)ix->orbit)->gblk >= 1024));
+    // each distinct tile searched once (see ft_dedup_hash_kernel); the query kernels read through a permutation on
+    // the Haar path only
+    const int dd_mode = g_ft_dedup.load(std::memory_order_relaxed);
+    const bool dedup = dd_mode != 0 && use_wavelets && Q >= 8192;
+    if (group || dedup) {
+        const int nb = (Q + 255) / 256;
+        if ((size_t)Q > s.cap_flat) {
+            if (s.fperm || s.fbcnt || s.fflag || s.fidx || s.ferr || s.ftile || s.fpal || s.fhm || s.fvm || s.dslot ||
+                s.drep || s.dpos)
+                (void)hipDeviceSynchronize();  // (as above)
+            dfree(s.fperm);
+            dfree(s.fbcnt);
+            dfree(s.fflag);
+            dfree(s.fidx);
+            dfree(s.ferr);
+            dfree(s.ftile);
+            dfree(s.fpal);
+            dfree(s.fhm);
+            dfree(s.fvm);
+            dfree(s.dslot);
+            dfree(s.drep);
+            dfree(s.dpos);
+            s.fperm = s.fbcnt = s.fidx = nullptr;  // a failed allocation below leaves nothing dangling
+            s.fflag = s.fhm = s.fvm = nullptr;
+            s.ferr = nullptr;
+            s.ftile = s.fpal = nullptr;
+            s.dslot = s.drep = s.dpos = nullptr;
+            s.cap_flat = 0;
+            if (!s.fcnt) TILER_HIP_CHECK(dmalloc((void **)&s.fcnt, 4 * sizeof(int)));
+            TILER_HIP_CHECK(dmalloc((void **)&s.fperm, (size_t)Q * sizeof(int)));
+            TILER_HIP_CHECK(dmalloc((void **)&s.fbcnt, (size_t)3 * nb * sizeof(int)));
+            TILER_HIP_CHECK(dmalloc((void **)&s.fflag, (size_t)Q));
+            TILER_HIP_CHECK(dmalloc((void **)&s.fidx, (size_t)Q * sizeof(int)));
+            TILER_HIP_CHECK(dmalloc((void **)&s.ferr, (size_t)Q * sizeof(float)));
+            TILER_HIP_CHECK(dmalloc((void **)&s.ftile, (size_t)Q * sizeof(int32_t)));
+            TILER_HIP_CHECK(dmalloc((void **)&s.fpal, (size_t)Q * sizeof(int32_t)));
+            TILER_HIP_CHECK(dmalloc((void **)&s.fhm, (size_t)Q));
+            TILER_HIP_CHECK(dmalloc((void **)&s.fvm, (size_t)Q));
+            TILER_HIP_CHECK(dmalloc((void **)&s.dslot, (size_t)Q * sizeof(int)));
+            TILER_HIP_CHECK(dmalloc((void **)&s.drep, (size_t)Q * sizeof(int)));
+            TILER_HIP_CHECK(dmalloc((void **)&s.dpos, (size_t)Q * sizeof(int)));
+            s.cap_flat = Q;
+        }
+        int nq = Q;              // queries searched
+        bool engaged = false;    // the searched batch is the representatives
+        const int *cnt = s.fcnt; // device count of the searched batch's non-flat queries
+        if (dedup) {
+            size_t slots = 1;
+            while (slots < 2 * (size_t)Q) slots <<= 1;
+            if (slots > s.cap_tab) {
+                if (s.dkey || s.dmin) (void)hipDeviceSynchronize();  // (as above)
+                dfree(s.dkey);
+                dfree(s.dmin);
+                s.dkey = nullptr;
+                s.dmin = nullptr;
+                s.cap_tab = 0;
+                TILER_HIP_CHECK(dmalloc((void **)&s.dkey, slots * sizeof(unsigned long long)));
+                TILER_HIP_CHECK(dmalloc((void **)&s.dmin, slots * sizeof(unsigned int)));
+                s.cap_tab = slots;
             }
+            if (!ix->h_ft_cnt && !(ix->h_ft_cnt = pinned_slot())) {
+                set_error("frame tiling: pinned host allocation failed");
+                return -1;
+            }
+            {
+                KTimer tm("ft_dedup", stream);
+                TILER_HIP_CHECK(hipMemsetAsync(s.dkey, 0xff, slots * sizeof(unsigned long long), stream));
+                TILER_HIP_CHECK(hipMemsetAsync(s.dmin, 0xff, slots * sizeof(unsigned int), stream));
+                hipLaunchKernelGGL(ft_dedup_hash_kernel, dim3(nb), dim3(256), 0, stream, d_rgb, Q,
+                                   dd_mode == 2 ? 15ull : ~0ull, s.dkey, s.dmin, (unsigned int)(slots - 1), s.fflag,
+                                   s.dslot);
+                hipLaunchKernelGGL(ft_dedup_rep_kernel, dim3(nb), dim3(256), 0, stream, d_rgb, Q,
+                                   (const unsigned int *)s.dmin, (const int *)s.dslot, (const uint8_t *)s.fflag, s.drep,
+                                   s.fbcnt, nb);
+                hipLaunchKernelGGL(ft_flat_scan_kernel, dim3(3), dim3(1024), 0, stream, s.fbcnt, nb, s.fcnt);
+                TILER_HIP_CHECK(hipGetLastError());
+                TILER_HIP_CHECK(hipMemcpyAsync(ix->h_ft_cnt, s.fcnt, 3 * sizeof(int), hipMemcpyDeviceToHost, stream));
+                // placed while the counts travel (wasted only on a batch without repeats)
+                hipLaunchKernelGGL(ft_dedup_place_kernel, dim3(nb), dim3(256), 0, stream, Q, (const uint8_t *)s.fflag,
+                                   (const int *)s.drep, (const int *)s.fbcnt, nb, (const int *)s.fcnt, s.fperm, s.dpos);
+                TILER_HIP_CHECK(hipGetLastError());
+            }
+            TILER_HIP_CHECK(hipStreamSynchronize(stream));  // this stream only: the launches below are sized by U
+            const int U = ix->h_ft_cnt[0] + ix->h_ft_cnt[1];
+            if (U < 1 || U > Q) {
+                set_error("frame tiling: inconsistent representative count");
+                return -1;
+            }
+            engaged = U <= Q - Q / 8;
+            if (engaged) {
+                nq = U;
+            } else if (group) {  // few repeats: today's grouping of all Q tiles, from the flags and counts above
+                cnt = s.fcnt + 2;
+                hipLaunchKernelGGL(ft_flat_place_kernel, dim3(nb), dim3(256), 0, stream, d_rgb, Q,
+                                   (const uint8_t *)s.fflag, (const int *)(s.fbcnt + (size_t)2 * nb), cnt, s.fperm);
+                TILER_HIP_CHECK(hipGetLastError());
+            }
+        } else {
             hipLaunchKernelGGL(ft_flat_flag_kernel, dim3(nb), dim3(256), 0, stream, d_rgb, Q, s.fflag, s.fbcnt);
             hipLaunchKernelGGL(ft_flat_scan_kernel, dim3(1), dim3(1024), 0, stream, s.fbcnt, nb, s.fcnt);
             hipLaunchKernelGGL(ft_flat_place_kernel, dim3(nb), dim3(256), 0, stream, d_rgb, Q, (const uint8_t *)s.fflag,
                                (const int *)s.fbcnt, (const int *)s.fcnt, s.fperm);
             TILER_HIP_CHECK(hipGetLastError());
+        }
+        if (engaged || group) {
             FtMaps fm;
             if (maps) fm = FtMaps{s.ftile, s.fpal, s.fhm, s.fvm};
-            ix->flat_cnt = s.fcnt;  // the shortlist reads the non-flat count on the device (no host sync)
+            // the shortlist reads the non-flat count on the device (no host sync)
+            ix->flat_cnt = group ? cnt : nullptr;
             int rc = 0;
-            if (flat_generic) {
+            if (!(ix->orbit && use_wavelets)) {
                 PsyvArgs pa;
-                pa.n = Q;
+                pa.n = nq;
                 pa.rgb = d_rgb;
                 pa.perm = s.fperm;
                 pa.flags = PSYV_WAVELETS;
@@ -2428,19 +2667,30 @@ int nn_frame_tiling_dev(NNIndex *ix, const int32_t *d_rgb, int Q, int use_wavele
                     pa.rootbox = s.kd_rootbox;
                 }
                 rc = launch_psyv(pa, stream);
-                if (!rc) rc = nn_search_dev(ix, s.qrows, Q, 1, s.fidx, s.ferr, maps ? &fm : nullptr, stream, fuse_rb);
+                if (!rc) rc = nn_search_dev(ix, s.qrows, nq, 1, s.fidx, s.ferr, maps ? &fm : nullptr, stream, fuse_rb);
             } else {
-                rc = orbit_ft_queries(ix, d_rgb, Q, gamma, s.qrows, fuse_rb ? ix->kd->d_box : nullptr,
+                rc = orbit_ft_queries(ix, d_rgb, nq, gamma, s.qrows, fuse_rb ? ix->kd->d_box : nullptr,
                                       fuse_rb ? s.kd_rootbox : nullptr, stream, s.fperm);
                 if (!rc)
-                    rc = nn_search_dev(ix, s.qrows, Q, 1, s.fidx, s.ferr, maps ? &fm : nullptr, stream, fuse_rb, true);
+                    rc = nn_search_dev(ix, s.qrows, nq, 1, s.fidx, s.ferr, maps ? &fm : nullptr, stream, fuse_rb, true);
             }
             ix->flat_cnt = nullptr;
             if (rc) return -1;
-            hipLaunchKernelGGL(ft_unpermute_kernel, dim3(nb), dim3(256), 0, stream, Q, (const int *)s.fperm,
-                               (const int *)s.fidx, (const float *)s.ferr, (const int32_t *)s.ftile,
-                               (const int32_t *)s.fpal, (const uint8_t *)s.fhm, (const uint8_t *)s.fvm, d_idx, d_err,
-                               maps ? *maps : FtMaps{});
+            if (engaged) {
+                ix->last_queries = Q;
+                ix->last_dup = Q - nq;
+                ix->last_ft_nonflat = ix->h_ft_cnt[2];
+                KTimer tm("ft_dedup", stream);
+                hipLaunchKernelGGL(ft_dedup_scatter_kernel, dim3(nb), dim3(256), 0, stream, Q, (const int *)s.drep,
+                                   (const int *)s.dpos, (const int *)s.fidx, (const float *)s.ferr,
+                                   (const int32_t *)s.ftile, (const int32_t *)s.fpal, (const uint8_t *)s.fhm,
+                                   (const uint8_t *)s.fvm, d_idx, d_err, maps ? *maps : FtMaps{});
+            } else {
+                hipLaunchKernelGGL(ft_unpermute_kernel, dim3(nb), dim3(256), 0, stream, Q, (const int *)s.fperm,
+                                   (const int *)s.fidx, (const float *)s.ferr, (const int32_t *)s.ftile,
+                                   (const int32_t *)s.fpal, (const uint8_t *)s.fhm, (const uint8_t *)s.fvm, d_idx, d_err,
+                                   maps ? *maps : FtMaps{});
+            }
             TILER_HIP_CHECK(hipGetLastError());
             return 0;
         }

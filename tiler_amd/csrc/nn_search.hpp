@@ -50,13 +50,21 @@ struct SearchScratch {
     float *kd_rootbox = nullptr;  // [nq] annBoxDistance of each query to the kd-tree's enclosing box
     uint8_t *kd_done = nullptr;   // [nq] 1: the pair pass already checked this query's winner
     // FrameTiling: flat tiles moved last (their descriptors have only isotypic block 0)
-    int *fperm = nullptr, *fbcnt = nullptr, *fcnt = nullptr;  // [Q] new -> original, [blocks], [1] non-flat count
+    // fperm [Q]: new -> original; fbcnt [3][blocks]: per-block counts (non-flat representatives, flat representatives,
+    // the call's non-flat tiles; without dedupe only the first row, the non-flat tiles); fcnt [4]: their totals
+    int *fperm = nullptr, *fbcnt = nullptr, *fcnt = nullptr;
     uint8_t *fflag = nullptr;
     int *fidx = nullptr;
     float *ferr = nullptr;
     int32_t *ftile = nullptr, *fpal = nullptr;
     uint8_t *fhm = nullptr, *fvm = nullptr;
-    size_t cap_q = 0, cap_keys = 0, cap_rows = 0, cap_flat = 0;
+    // FrameTiling: each distinct tile of a call searched once (ft_dedup_* kernels).  dkey / dmin [cap_tab]: the call's
+    // hash table (key, smallest tile index of the key); dslot [Q]: a tile's table slot; drep [Q]: the tile whose
+    // result a tile takes (itself: a representative); dpos [Q]: a representative's position in the searched batch
+    unsigned long long *dkey = nullptr;
+    unsigned int *dmin = nullptr;
+    int *dslot = nullptr, *drep = nullptr, *dpos = nullptr;
+    size_t cap_q = 0, cap_keys = 0, cap_rows = 0, cap_flat = 0, cap_tab = 0;
 };
 
 struct NNIndex {
@@ -86,6 +94,11 @@ struct NNIndex {
     // stats are read from the device count (last_flat_dev) and the launch shape; 0 when the search had no flat grouping
     const int *last_flat_dev = nullptr;
     long last_flat_nq = 0, last_flat_qpw = 0, last_flat_wgs = 0;
+    // a FrameTiling call that searched its distinct tiles only (nn_frame_tiling_dev): last_queries is the call's Q,
+    // last_searched the representatives, last_dup = Q - last_searched, last_ft_nonflat the call's non-flat tiles
+    // (duplicates included; -1: no such call) from which flat_queries is reported in the call's own units
+    long long last_searched = 0, last_dup = 0, last_ft_nonflat = -1;
+    int *h_ft_cnt = nullptr;    // pinned [4]: the dedupe counts read back inside the call
     hipEvent_t done_event = nullptr;  // recorded at the end of every search on its stream (stats wait on it)
     int last_orbit = 0;         // 1: the last search ran the mirror-orbit path
     OrbitIndex *orbit = nullptr; // mirror-orbit index (orbit.hip), null when not applicable
@@ -122,6 +135,8 @@ void nn_set_scan_limits(int max_k1, int max_k8);
 // test hook: every kd pruning check lists its query for the exact replay (results unchanged)
 void nn_set_force_replay(int on);
 void nn_set_shortlist_gate(int on);
+// tiler_debug_ft_dedup: 1 (default) distinct tiles of a FrameTiling call searched once, 0 off, 2 on with a 4-bit hash
+void nn_set_ft_dedup(int mode);
 
 // frame tiling: RGB tiles -> descriptors (fp32) -> search -> tilemap items
 int nn_frame_tiling_dev(NNIndex *ix, const int32_t *d_rgb, int Q, int use_wavelets, int gamma, int *d_idx,

@@ -169,6 +169,31 @@ def test_degenerate_layouts(gpu, orbit_case, name):
         assert (np.asarray(g[0]) == np.asarray(g[0])[0]).all()
 
 
+@pytest.fixture(scope="module")
+def orbit_per_frame(orbit_case):
+    """The per-frame-call outputs of the module's 9,600 rows (8 calls of 1,200, all below the threshold), once."""
+    return _per_frame(orbit_case["kt"], orbit_case["frames"])
+
+
+@pytest.mark.parametrize("mode", [1, 0])
+def test_scratch_growth_on_one_handle(gpu, orbit_case, orbit_per_frame, mode):
+    """8,192 tiles, then 12,288 (both buffer groups and the hash table outgrown), then 8,192 again (inside the larger
+    capacities) on one handle: every call equals the per-frame calls of its rows byte for byte.  A tile's outputs
+    depend on its own words only, so the per-frame outputs of a row set are those rows of orbit_per_frame."""
+    rows, kt = orbit_case["rows"], orbit_case["kt"]
+    for pick in (np.arange(8192), np.concatenate([np.arange(9600), np.arange(2688)]), np.arange(8192)):
+        r = np.ascontiguousarray(rows[pick])
+        Q, distinct = r.shape[0], _distinct(r)
+        assert distinct <= Q - Q // 8  # enough repeats for the dedupe to engage
+        got, st = _run(gpu, kt, r, mode)
+        _same(got, [a[pick] for a in orbit_per_frame], f"{Q} tiles, mode {mode}")
+        assert st["queries"] == Q
+        if mode == 1:
+            assert st["searched_queries"] == distinct and st["dup_queries"] == Q - distinct
+        else:
+            assert st["searched_queries"] == Q and st["dup_queries"] == 0
+
+
 def test_not_engaged_without_repeats(gpu, orbit_case):
     """9,600 distinct tiles: the call pays the three passes and then runs as with the switch off."""
     kt = orbit_case["kt"]

@@ -799,9 +799,13 @@ static int combine_run(ann_kdtree *t, CombineSlot &cs, std::vector<CombineReq *>
     const bool small = nn_search_is_small(ix, nq, k);
     int *hd_res = nullptr;  // the device's view of h_res (a small-batch scan writes its results there: no copy back)
     TILER_HIP_CHECK(hipHostGetDevicePointer((void **)&hd_res, cs.h_res, 0));
+    SearchOpts so;
+    if (small) {
+        so.h_idx = hd_res;
+        so.h_err = reinterpret_cast<float *>(hd_res + nr);
+    }
     std::swap(ix->scratch, cs.scratch);  // this batch's scratch
-    const int rc = nn_search_dev(ix, cs.d_q, nq, k, r_idx, r_err, nullptr, cs.stream, false, false,
-                                 small ? hd_res : nullptr, small ? reinterpret_cast<float *>(hd_res + nr) : nullptr);
+    const int rc = nn_search_dev(ix, cs.d_q, nq, k, r_idx, r_err, nullptr, cs.stream, so);
     std::swap(ix->scratch, cs.scratch);
     if (rc) return -1;
     if (!small)
@@ -1103,11 +1107,11 @@ int ann_kdtree_get_stats(ann_kdtree *t, tiler_search_stats *out) {
     std::lock_guard<std::mutex> lk(t->ix->mu);
     // everything below was written by the last search on ITS stream (the caller's, for the _dev entry points)
     if (t->ix->done_event) TILER_HIP_CHECK(hipEventSynchronize(t->ix->done_event));
-    out->queries = t->ix->last_queries;
-    out->fallback_queries = t->ix->last_splits > 0 ? t->ix->h_fb_count[0] : 0;
-    out->exhaustive_queries = t->ix->last_splits > 0 ? t->ix->h_fb_count[1] : t->ix->last_fallback;
+    out->queries = t->ix->last.queries;
+    out->fallback_queries = t->ix->last.splits > 0 ? t->ix->h_fb_count[0] : 0;
+    out->exhaustive_queries = t->ix->last.splits > 0 ? t->ix->h_fb_count[1] : t->ix->last.fallback;
     out->exact_integer = t->ix->exact_int ? 1 : 0;
-    out->splits = t->ix->last_splits;
+    out->splits = t->ix->last.splits;
     out->orbit_groups = t->ix->orbit ? orbit_groups(t->ix) : 0;
     out->orbit_search = t->ix->last_orbit;
     out->orbit_ksteps = t->ix->orbit ? orbit_ksteps(t->ix) : 0;
@@ -1120,18 +1124,18 @@ int ann_kdtree_get_stats(ann_kdtree *t, tiler_search_stats *out) {
     out->kd_build_ms = t->ix->kd ? t->ix->kd->build_ms : 0.0;
     out->kd_replayed = 0;
     out->flat_queries = 0;
-    out->searched_queries = t->ix->last_searched;
+    out->searched_queries = t->ix->last.searched;
     out->searched_flat_queries = 0;
-    out->dup_queries = t->ix->last_dup;
-    if (const NNIndex *ix = t->ix; ix->last_flat_dev) {  // queries in all-flat shortlist workgroups
+    out->dup_queries = t->ix->last.dup;
+    if (const NNIndex *ix = t->ix; ix->last.flat_dev) {  // queries in all-flat shortlist workgroups
         int others = 0;
-        TILER_HIP_CHECK(hipMemcpy(&others, ix->last_flat_dev, sizeof(int), hipMemcpyDeviceToHost));
-        const long wf0 = std::min(ix->last_flat_wgs, (others + ix->last_flat_qpw - 1) / ix->last_flat_qpw);
-        out->searched_flat_queries = wf0 < ix->last_flat_wgs ? ix->last_flat_nq - wf0 * ix->last_flat_qpw : 0;
+        TILER_HIP_CHECK(hipMemcpy(&others, ix->last.flat_dev, sizeof(int), hipMemcpyDeviceToHost));
+        const long wf0 = std::min(ix->last.flat_wgs, (others + ix->last.flat_qpw - 1) / ix->last.flat_qpw);
+        out->searched_flat_queries = wf0 < ix->last.flat_wgs ? ix->last.flat_nq - wf0 * ix->last.flat_qpw : 0;
         out->flat_queries = out->searched_flat_queries;
-        if (ix->last_ft_nonflat >= 0) {  // distinct tiles searched: the same layout over the call's own tiles
-            const long qpw = ix->last_flat_qpw, Q = (long)ix->last_queries;
-            const long wgs = (Q + qpw - 1) / qpw, w0 = std::min(wgs, ((long)ix->last_ft_nonflat + qpw - 1) / qpw);
+        if (ix->last.ft_nonflat >= 0) {  // distinct tiles searched: the same layout over the call's own tiles
+            const long qpw = ix->last.flat_qpw, Q = (long)ix->last.queries;
+            const long wgs = (Q + qpw - 1) / qpw, w0 = std::min(wgs, ((long)ix->last.ft_nonflat + qpw - 1) / qpw);
             out->flat_queries = w0 < wgs ? Q - w0 * qpw : 0;
         }
     }

@@ -105,6 +105,28 @@ void dfree_sync(void *p) {
     dfree(p);
 }
 
+hipError_t dregrow(std::initializer_list<DevBuf> bufs, bool alloc, bool idle) {
+    bool held = false;
+    for (const DevBuf &b : bufs) held = held || *b.p;
+    if (held && !idle) (void)hipDeviceSynchronize();
+    auto release = [&] {
+        for (const DevBuf &b : bufs) {
+            dfree(*b.p);
+            *b.p = nullptr;
+        }
+    };
+    release();
+    if (!alloc) return hipSuccess;
+    for (const DevBuf &b : bufs) {
+        const hipError_t e = dmalloc(b.p, b.bytes);
+        if (e != hipSuccess) {
+            release();  // (blocks dmalloc has just handed out are idle)
+            return e;
+        }
+    }
+    return hipSuccess;
+}
+
 // Streams and pinned count slots of the per-keyframe handles, reused the same way (a stream create / destroy pair and
 // a small pinned allocation + free are further driver calls per keyframe).
 namespace {

@@ -29,7 +29,6 @@
 #include "nn_dev.hpp"
 #include "orbit.hpp"
 #include "orbit_map_gen.hpp"
-#include "psyv.hpp"
 
 #pragma clang fp contract(off)
 
@@ -1666,43 +1665,47 @@ NNIndex *nn_index_create_dev(float *d_rows, int n, int d, int bs, int split, hip
     return ix;
 }
 
+static constexpr int TIER2_MAX = 65536;  // generic tier 2: queries per collect chunk (every tier-2 query has a slot)
+static constexpr int TIER2_CAP = 1024;   // generic tier 2: collected candidates per query (beyond: tier 3)
+
+// The scratch's three buffer groups, each sized in one place (0: released; idle: the caller has waited for the device).
+static hipError_t scratch_size_queries(SearchScratch &s, size_t nq, bool idle = false) {
+    s.cap_q = 0;
+    hipError_t e = dregrow({{s.qfrag, ((nq + 31) / 32 + 2) * 16 * 64 * 16},
+                            {s.qfrag16, ((nq + 15) / 16 + 2) * 8 * 64 * 16},
+                            {s.qstat, nq * sizeof(QStat)},
+                            {s.fb_list, nq * sizeof(int)},
+                            {s.fb_count, 16},
+                            {s.thr, nq * sizeof(float)},
+                            {s.gate, nq * sizeof(float2)},
+                            {s.ex_list, nq * sizeof(int)},
+                            {s.kd_list, nq * sizeof(int)},
+                            {s.kd_rootbox, nq * sizeof(float)},
+                            {s.kd_done, nq},
+                            {s.t2best, nq * sizeof(unsigned long long)}},
+                           nq > 0, idle);
+    // (the replay count keeps its block and its value across growth: the statistics read it after any search)
+    if (nq == 0) (void)dregrow({{s.kd_count, 0}}, false, idle);
+    else if (e == hipSuccess && !s.kd_count) e = dmalloc((void **)&s.kd_count, 16);
+    if (e == hipSuccess) s.cap_q = nq;
+    return e;
+}
+static hipError_t scratch_size_keys(SearchScratch &s, size_t nkeys, bool idle = false) {
+    s.cap_keys = 0;
+    const hipError_t e = dregrow({{s.key, nkeys * sizeof(float)}, {s.idx, nkeys * sizeof(int)}}, nkeys > 0, idle);
+    if (e == hipSuccess) s.cap_keys = nkeys;
+    return e;
+}
+// the generic tier 2's collect buffers (256 MB): made by the first search that can need them
+static hipError_t scratch_size_collect(SearchScratch &s, bool on, bool idle = false) {
+    return dregrow({{s.ccnt, (size_t)TIER2_MAX * sizeof(int)}, {s.cbuf, (size_t)TIER2_MAX * TIER2_CAP * sizeof(int)}},
+                   on, idle);
+}
+
 void nn_scratch_free(SearchScratch &s, bool synced) {
-    if (!synced && (s.qfrag || s.key || s.qrows || s.ccnt || s.fperm || s.kd_count))
-        (void)hipDeviceSynchronize();  // dfree files the blocks for reuse: nothing may still read them (hipFree's rule)
-    dfree(s.qfrag);
-    dfree(s.qfrag16);
-    dfree(s.qstat);
-    dfree(s.key);
-    dfree(s.idx);
-    dfree(s.fb_list);
-    dfree(s.fb_count);
-    dfree(s.qrows);
-    dfree(s.thr);
-    dfree(s.gate);
-    dfree(s.ex_list);
-    dfree(s.ccnt);
-    dfree(s.cbuf);
-    dfree(s.kd_list);
-    dfree(s.kd_count);
-    dfree(s.kd_rootbox);
-    dfree(s.kd_done);
-    dfree(s.t2best);
-    dfree(s.fperm);
-    dfree(s.fbcnt);
-    dfree(s.fcnt);
-    dfree(s.fflag);
-    dfree(s.fidx);
-    dfree(s.ferr);
-    dfree(s.ftile);
-    dfree(s.fpal);
-    dfree(s.fhm);
-    dfree(s.fvm);
-    dfree(s.dkey);
-    dfree(s.dmin);
-    dfree(s.dslot);
-    dfree(s.drep);
-    dfree(s.dpos);
-    s = SearchScratch();
+    (void)scratch_size_queries(s, 0, synced);
+    (void)scratch_size_keys(s, 0, synced);
+    (void)scratch_size_collect(s, false, synced);
 }
 
 void nn_index_destroy(NNIndex *ix) {
@@ -1721,73 +1724,22 @@ void nn_index_destroy(NNIndex *ix) {
     dfree(ix->d_tr_pal);
     dfree(ix->d_tr_attr);
     nn_scratch_free(ix->scratch, true);
+    ft_scratch_free(ix->ft);
     pinned_slot_free(ix->h_fb_count);
-    pinned_slot_free(ix->h_ft_cnt);
     if (ix->done_event) hipEventDestroy(ix->done_event);
     delete ix;
 }
 
-static constexpr int TIER2_MAX = 65536;  // generic tier 2: queries per collect chunk (every tier-2 query has a slot)
-static constexpr int TIER2_CAP = 1024;   // generic tier 2: collected candidates per query (beyond: tier 3)
-
+// A handle's first call has nothing to file, so dregrow waits for nothing there: a device-wide wait would also wait
+// for other streams' work (the encoder's next Prepare, running beside this FrameTiling).
 static int ensure_scratch(NNIndex *ix, long nq, long nkeys) {
     SearchScratch &s = ix->scratch;
-    // the outgrown buffers go back to the block cache: earlier searches must be done.  A handle's first call has
-    // nothing to file, and a device-wide wait there would also wait for other streams' work (the encoder's next
-    // Prepare, running beside this FrameTiling)
-    const bool q_held = s.qfrag || s.qfrag16 || s.qstat || s.fb_list || s.fb_count || s.thr || s.gate || s.ex_list ||
-                        s.kd_list || s.kd_rootbox || s.kd_done || s.t2best;
-    if (((size_t)nq > s.cap_q && q_held) || ((size_t)nkeys > s.cap_keys && (s.key || s.idx)))
-        (void)hipDeviceSynchronize();
-    if ((size_t)nq > s.cap_q) {
-        dfree(s.qfrag);
-        dfree(s.qfrag16);
-        dfree(s.qstat);
-        dfree(s.fb_list);
-        dfree(s.fb_count);
-        dfree(s.thr);
-        dfree(s.gate);
-        dfree(s.ex_list);
-        dfree(s.kd_list);
-        dfree(s.kd_rootbox);
-        dfree(s.kd_done);
-        dfree(s.t2best);
-        s.qfrag = s.qfrag16 = nullptr;
-        s.qstat = nullptr;
-        s.fb_list = s.fb_count = s.ex_list = s.kd_list = nullptr;
-        s.thr = s.kd_rootbox = nullptr;
-        s.gate = nullptr;
-        s.kd_done = nullptr;
-        s.t2best = nullptr;
-        s.cap_q = 0;
-        const long nqblk = (nq + 31) / 32 + 2;
-        TILER_HIP_CHECK(dmalloc(&s.qfrag, (size_t)nqblk * 16 * 64 * 16));
-        TILER_HIP_CHECK(dmalloc(&s.qfrag16, (size_t)((nq + 15) / 16 + 2) * 8 * 64 * 16));
-        TILER_HIP_CHECK(dmalloc((void **)&s.qstat, (size_t)nq * sizeof(QStat)));
-        TILER_HIP_CHECK(dmalloc((void **)&s.fb_list, (size_t)nq * sizeof(int)));
-        TILER_HIP_CHECK(dmalloc((void **)&s.fb_count, 16));
-        TILER_HIP_CHECK(dmalloc((void **)&s.thr, (size_t)nq * sizeof(float)));
-        TILER_HIP_CHECK(dmalloc((void **)&s.gate, (size_t)nq * sizeof(float2)));
-        TILER_HIP_CHECK(dmalloc((void **)&s.ex_list, (size_t)nq * sizeof(int)));
-        TILER_HIP_CHECK(dmalloc((void **)&s.kd_list, (size_t)nq * sizeof(int)));
-        TILER_HIP_CHECK(dmalloc((void **)&s.kd_rootbox, (size_t)nq * sizeof(float)));
-        TILER_HIP_CHECK(dmalloc((void **)&s.kd_done, (size_t)nq));
-        TILER_HIP_CHECK(dmalloc((void **)&s.t2best, (size_t)nq * sizeof(unsigned long long)));
-        s.cap_q = nq;
-    }
-    if (!s.kd_count) TILER_HIP_CHECK(dmalloc((void **)&s.kd_count, 16));
-    if ((size_t)nkeys > s.cap_keys) {
-        dfree(s.key);
-        dfree(s.idx);
-        s.key = nullptr;
-        s.idx = nullptr;
-        s.cap_keys = 0;
-        TILER_HIP_CHECK(dmalloc((void **)&s.key, (size_t)nkeys * sizeof(float)));
-        TILER_HIP_CHECK(dmalloc((void **)&s.idx, (size_t)nkeys * sizeof(int)));
-        s.cap_keys = nkeys;
-    }
+    if ((size_t)nq > s.cap_q) TILER_HIP_CHECK(scratch_size_queries(s, nq));
+    if ((size_t)nkeys > s.cap_keys) TILER_HIP_CHECK(scratch_size_keys(s, nkeys));
     return 0;
 }
+
+int nn_ensure_rootbox(NNIndex *ix, int nq) { return ensure_scratch(ix, nq, 0); }
 
 // waves per workgroup of the 32x32x16 shortlist on 64-d rows (UseOne's k = 8 preselection, main.pas:3830): two query
 // blocks of 32 per wave, so 64 * NW queries per workgroup
@@ -1831,9 +1783,11 @@ static int shortlist16_L() {
     const int v = shortlist_variant();
     return v == 16 ? 4 : v == 166 ? 6 : 0;
 }
+bool nn_generic_takes_flat(const NNIndex *ix) { return ix->S16 > 0 && shortlist16_L() > 0; }
 
 template <int S, int L>
-static int launch_shortlist16(NNIndex *ix, int nq, int nsplit, int bps, bool gated, hipStream_t stream) {
+static int launch_shortlist16(NNIndex *ix, int nq, int nsplit, int bps, bool gated, const int *flat_cnt,
+                              hipStream_t stream) {
     const int nqblk = (nq + 15) / 16;
     const dim3 grid((nqblk + SL16_NW * SL16_QB - 1) / (SL16_NW * SL16_QB), nsplit);
     const size_t buf = SL16_CB * S * 1024 + SL16_CB * 64;
@@ -1850,17 +1804,17 @@ static int launch_shortlist16(NNIndex *ix, int nq, int nsplit, int bps, bool gat
     auto go = [&](auto kern, int nbuf) {
         hipLaunchKernelGGL(kern, grid, dim3(SL16_NW * 64), nbuf * buf, stream, (const half8 *)ix->d_frag16,
                            ix->d_seed16, ix->nblk16, (const half8 *)ix->scratch.qfrag16, nq, bps, nsplit, ix->perm,
-                           ix->scratch.key, ix->scratch.idx, ix->flat_cnt, gated ? (const float2 *)ix->scratch.gate : nullptr,
+                           ix->scratch.key, ix->scratch.idx, flat_cnt, gated ? (const float2 *)ix->scratch.gate : nullptr,
                            gb);
     };
     KTimer tm("nn_shortlist", stream);
     go(nn_shortlist16_kernel<S, L, SL16_CB, SL16_NW, SL16_QB, 0, SL16_VAR>, 2);
     TILER_HIP_CHECK(hipGetLastError());
-    if (ix->flat_cnt) {  // flat_queries of the stats: derived from the device count when they are read
-        ix->last_flat_dev = ix->flat_cnt;
-        ix->last_flat_nq = nq;
-        ix->last_flat_qpw = SL16_NW * SL16_QB * 16;
-        ix->last_flat_wgs = grid.x;
+    if (flat_cnt) {  // flat_queries of the stats: derived from the device count when they are read
+        ix->last.flat_dev = flat_cnt;
+        ix->last.flat_nq = nq;
+        ix->last.flat_qpw = SL16_NW * SL16_QB * 16;
+        ix->last.flat_wgs = grid.x;
     }
     return 0;
 }
@@ -1948,12 +1902,12 @@ static int tier2_slots(NNIndex *ix, int nq) {
     return (int)std::min<long>(nq, chunks * TIER2_MAX);
 }
 static int search_core(NNIndex *ix, RescoreArgs &ra, const float *d_q, int nq, int k, hipStream_t stream,
-                       bool orbit_prepared);
+                       const SearchOpts &opt);
 static bool scan_small_takes(const NNIndex *ix, int nq, int k);
 static std::atomic<int> g_force_replay{0};  // tiler_debug_force_replay
 
 int nn_search_dev(NNIndex *ix, const float *d_q, int nq, int k, int *d_idx, float *d_err, const FtMaps *maps,
-                  hipStream_t stream, bool rootbox_ready, bool orbit_prepared, int *h_idx, float *h_err) {
+                  hipStream_t stream, const SearchOpts &opt) {
     if (nq <= 0) return 0;
     if (k < 1 || k > 32) {
         set_error("nn: k must be in 1..32");
@@ -1974,8 +1928,8 @@ int nn_search_dev(NNIndex *ix, const float *d_q, int nq, int k, int *d_idx, floa
     ra.out_idx = d_idx;
     ra.out_err = d_err;
     ra.ko = ix->kd ? ix->kd->d_view : nullptr;
-    ra.h_idx = h_idx;
-    ra.h_err = h_idx ? h_err : nullptr;
+    ra.h_idx = opt.h_idx;
+    ra.h_err = opt.h_idx ? opt.h_err : nullptr;
     if (maps && k == 1 && ix->d_tr_tile) {
         ra.tr_tile = ix->d_tr_tile;
         ra.tr_pal = ix->d_tr_pal;
@@ -1985,31 +1939,28 @@ int nn_search_dev(NNIndex *ix, const float *d_q, int nq, int k, int *d_idx, floa
         ra.m_hm = maps->hm;
         ra.m_vm = maps->vm;
     }
-    ix->last_queries = nq;
-    ix->last_searched = nq;
-    ix->last_dup = 0;
-    ix->last_ft_nonflat = -1;
-    ix->last_flat_dev = nullptr;
+    ix->last = LastSearch();
+    ix->last.queries = ix->last.searched = nq;
     SearchScratch &s = ix->scratch;
     if (!ix->done_event) TILER_HIP_CHECK(hipEventCreateWithFlags(&ix->done_event, hipEventDisableTiming));
     if (ix->kd && scan_small_takes(ix, nq, k)) {  // the coalesced per-tile batches: scan, merge + pruning check, replay
         if (ensure_scratch(ix, nq, 0)) return -1;
         ra.prune = ix->kd->n > ix->kd->bs;  // a single bucket: no pruning, position order is exact
         ra.force_replay = g_force_replay.load(std::memory_order_relaxed);
-        if (search_core(ix, ra, d_q, nq, k, stream, orbit_prepared)) return -1;
+        if (search_core(ix, ra, d_q, nq, k, stream, opt)) return -1;
         TILER_HIP_CHECK(hipEventRecord(ix->done_event, stream));
         return 0;
     }
     if (ix->kd) {  // ANN's tie order: the pruning check needs every query's box distance and a clean slate
         if (ensure_scratch(ix, nq, 0)) return -1;
-        if (!rootbox_ready) {  // the box distances, with the verify flags and the replay count cleared in the same launch
+        if (!opt.rootbox_ready) {  // the box distances, with the verify flags and the replay count cleared in the same launch
             if (kd_root_boxes(ix->kd, d_q, nq, s.kd_rootbox, stream, s.kd_done, s.kd_count)) return -1;
         } else {
             TILER_HIP_CHECK(hipMemsetAsync(s.kd_done, 0, (size_t)nq, stream));
             TILER_HIP_CHECK(hipMemsetAsync(s.kd_count, 0, sizeof(int), stream));
         }
     }
-    if (search_core(ix, ra, d_q, nq, k, stream, orbit_prepared)) return -1;
+    if (search_core(ix, ra, d_q, nq, k, stream, opt)) return -1;
     if (!ix->kd) {
         TILER_HIP_CHECK(hipEventRecord(ix->done_event, stream));
         return 0;
@@ -2080,8 +2031,8 @@ static int scan_small(NNIndex *ix, RescoreArgs &ra, int nq, int k, hipStream_t s
     }
     if (ensure_scratch(ix, nq, (long)nq * nsplit * K)) return -1;
     SearchScratch &s = ix->scratch;
-    ix->last_splits = 0;  // the stats report no tier-2 / tier-3 queries for a scan (fb_count is not read)
-    ix->last_fallback = 0;
+    ix->last.splits = 0;  // the stats report no tier-2 / tier-3 queries for a scan (fb_count is not read)
+    ix->last.fallback = 0;
     KTimer tm("nn_scan", stream);
     // the per-query work is unrolled over QN: the smallest instance that holds a group
     const int qn = K == 1 ? (nq == 1 ? 1 : nq <= 4 ? 4 : SCAN_QN1) : (nq == 1 ? 1 : SCAN_QN8);
@@ -2123,12 +2074,12 @@ static int scan_small(NNIndex *ix, RescoreArgs &ra, int nq, int k, hipStream_t s
 }
 
 static int search_core(NNIndex *ix, RescoreArgs &ra, const float *d_q, int nq, int k, hipStream_t stream,
-                       bool orbit_prepared) {
+                       const SearchOpts &opt) {
     if (scan_small_takes(ix, nq, k)) return scan_small(ix, ra, nq, k, stream);
     const bool mfma = ix->S > 0 && k <= 8;
     if (!mfma) {
-        ix->last_splits = 0;
-        ix->last_fallback = nq;
+        ix->last.splits = 0;
+        ix->last.fallback = nq;
         ra.ex_list = nullptr;
         return launch_exact(ra, nq, std::min(nq, 4096), stream);
     }
@@ -2145,7 +2096,7 @@ static int search_core(NNIndex *ix, RescoreArgs &ra, const float *d_q, int nq, i
     nsplit = std::min(nsplit, nblk);
     const int bps = (nblk + nsplit - 1) / nsplit;
     nsplit = (nblk + bps - 1) / bps;
-    ix->last_splits = nsplit;
+    ix->last.splits = nsplit;
     if (ensure_scratch(ix, nq, (long)nq * nsplit * lpq * L)) return -1;
     SearchScratch &s = ix->scratch;
     TILER_HIP_CHECK(hipMemsetAsync(s.fb_count, 0, 16, stream));
@@ -2160,7 +2111,7 @@ static int search_core(NNIndex *ix, RescoreArgs &ra, const float *d_q, int nq, i
         t.fb_max = nq;
         t.thr = s.thr;
         t.t2_best = s.t2best;
-        t.flat_cnt = ix->flat_cnt;
+        t.flat_cnt = opt.flat_cnt;
         t.out_idx = ra.out_idx;
         t.out_err = ra.out_err;
         t.tr_tile = ra.tr_tile;
@@ -2175,7 +2126,7 @@ static int search_core(NNIndex *ix, RescoreArgs &ra, const float *d_q, int nq, i
         t.kd_done = s.kd_done;
         t.kd_list = s.kd_list;
         t.kd_count = s.kd_count;
-        if (orbit_search(ix, d_q, nq, t, stream, orbit_prepared && k == 1)) return -1;
+        if (orbit_search(ix, d_q, nq, t, stream, opt.orbit_prepared && k == 1)) return -1;
         ix->last_orbit = 1;
         ra.qstat = s.qstat;
         ra.fb_list = s.fb_list;
@@ -2204,7 +2155,8 @@ static int search_core(NNIndex *ix, RescoreArgs &ra, const float *d_q, int nq, i
         }
         TILER_HIP_CHECK(hipGetLastError());
         {
-            if (launch_shortlist16<6, 4>(ix, nq, nsplit, bps, k == 1 && g_gate16.load(std::memory_order_relaxed), stream))
+            if (launch_shortlist16<6, 4>(ix, nq, nsplit, bps, k == 1 && g_gate16.load(std::memory_order_relaxed),
+                                         opt.flat_cnt, stream))
                 return -1;
         }
     } else if (dispatch_shortlist<8>(ix, nq, nsplit, bps, stream)) {
@@ -2221,10 +2173,7 @@ static int search_core(NNIndex *ix, RescoreArgs &ra, const float *d_q, int nq, i
     ra.ex_list = s.ex_list;
     ra.ex_count = s.fb_count + 1;
     ra.thr = s.thr;
-    if (!s.ccnt) {  // the generic tier 2's collect buffers (256 MB), on the first search that can need them
-        TILER_HIP_CHECK(dmalloc((void **)&s.ccnt, (size_t)TIER2_MAX * sizeof(int)));
-        TILER_HIP_CHECK(dmalloc((void **)&s.cbuf, (size_t)TIER2_MAX * TIER2_CAP * sizeof(int)));
-    }
+    if (!s.ccnt) TILER_HIP_CHECK(scratch_size_collect(s, true));
     ra.ccnt = s.ccnt;
     ra.cbuf = s.cbuf;
     ra.cap = TIER2_CAP;
@@ -2270,450 +2219,6 @@ static int search_tail(NNIndex *ix, const RescoreArgs &ra, int nq, hipStream_t s
         if (c >= 0 && c < (1 << 30)) g_t2_recent.store(c, std::memory_order_relaxed);
     }
     return 0;
-}
-
-// Flat tiles (one colour: every Haar coefficient but the DC is 0, so only isotypic block 0 of q' is nonzero) are
-// moved to the end of the batch, where whole shortlist workgroups of them run 3 of the 12 k-steps (orbit_search).
-// A: per tile flag + per-block count of the others; B: one workgroup scans the block counts; C: stable positions
-// (others first, flats after, each in tile order), which the query kernel reads through; D: the outputs back.
-__global__ __launch_bounds__(256) void ft_flat_flag_kernel(const int32_t *__restrict__ rgb, int Q, uint8_t *flag,
-                                                           int *bcnt) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    int other = 0;
-    if (i < Q) {
-        const int4 *t = reinterpret_cast<const int4 *>(rgb + i * 64);
-        const int c0 = rgb[i * 64];
-        bool flat = true;
-#pragma unroll
-        for (int k = 0; k < 16; k++) {
-            const int4 v = t[k];
-            flat = flat && v.x == c0 && v.y == c0 && v.z == c0 && v.w == c0;
-        }
-        flag[i] = flat ? 1 : 0;
-        other = flat ? 0 : 1;
-    }
-    const int c = __syncthreads_count(other);
-    if (threadIdx.x == 0) bcnt[blockIdx.x] = c;
-}
-
-// (one workgroup per row of counts: bcnt [gridDim.x][nb], total [gridDim.x])
-__global__ __launch_bounds__(1024) void ft_flat_scan_kernel(int *bcnt, int nb, int *total) {
-    __shared__ int sc[1024];
-    __shared__ int carry;
-    bcnt += (size_t)blockIdx.x * nb;
-    total += blockIdx.x;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < nb; b0 += 1024) {
-        const int b = b0 + threadIdx.x;
-        const int v = b < nb ? bcnt[b] : 0;
-        sc[threadIdx.x] = v;
-        __syncthreads();
-        for (int o = 1; o < 1024; o <<= 1) {
-            const int u = threadIdx.x >= o ? sc[threadIdx.x - o] : 0;
-            __syncthreads();
-            sc[threadIdx.x] += u;
-            __syncthreads();
-        }
-        if (b < nb) bcnt[b] = carry + sc[threadIdx.x] - v;  // exclusive prefix
-        __syncthreads();
-        if (threadIdx.x == 1023) carry += sc[1023];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-
-__global__ __launch_bounds__(256) void ft_flat_place_kernel(const int32_t *__restrict__ rgb, int Q,
-                                                            const uint8_t *__restrict__ flag,
-                                                            const int *__restrict__ boff, const int *__restrict__ total,
-                                                            int *perm) {
-    __shared__ int sc[256];
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    const int f = i < Q ? flag[i] : 1;
-    sc[threadIdx.x] = f ? 0 : 1;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-        const int u = threadIdx.x >= o ? sc[threadIdx.x - o] : 0;
-        __syncthreads();
-        sc[threadIdx.x] += u;
-        __syncthreads();
-    }
-    if (i >= Q) return;
-    const int rank_other = sc[threadIdx.x] - (f ? 0 : 1);          // others before this tile in the block
-    const int rank_flat = (int)threadIdx.x - rank_other - (f ? 0 : 1);  // flats before it in the block
-    const int b_other = boff[blockIdx.x], b_flat = (int)(blockIdx.x * 256) - b_other;
-    const long pos = f ? (long)*total + b_flat + rank_flat : (long)b_other + rank_other;
-    perm[pos] = (int)i;  // the query kernel reads tile perm[pos] (no copy of the RGB)
-}
-
-__global__ __launch_bounds__(256) void ft_unpermute_kernel(int Q, const int *__restrict__ perm, const int *fidx,
-                                                           const float *ferr, const int32_t *ftile, const int32_t *fpal,
-                                                           const uint8_t *fhm, const uint8_t *fvm, int *idx, float *err,
-                                                           FtMaps maps) {
-    const long p = (long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= Q) return;
-    const long o = perm[p];
-    if (idx) idx[o] = fidx[p];
-    if (err) err[o] = ferr[p];
-    if (maps.tile) maps.tile[o] = ftile[p];
-    if (maps.pal) maps.pal[o] = fpal[p];
-    if (maps.hm) maps.hm[o] = fhm[p];
-    if (maps.vm) maps.vm[o] = fvm[p];
-}
-
-// Each distinct tile of a call is searched once.  A tile's answer is a function of its 64 RGB words and the handle, and
-// a keyframe batch is consecutive frames of one shot, so most tiles repeat the tile at their position one frame
-// earlier.  Nothing outlives the call: the table is cleared, filled, verified and scattered from in every call.
-//   A (ft_dedup_hash_kernel): per tile the flat flag and a 64-bit hash of its words; the key claims a slot of the
-//      open-addressing table (64-bit CAS) and the slot keeps the smallest tile index of its key (atomicMin).  Which
-//      slot a key gets depends on the race, what a lookup returns does not.
-//   B (ft_dedup_rep_kernel): tile i reads its key's first index r; r == i: a representative; else all 64 words are
-//      compared with tile r's: equal -> rep_of[i] = r (r is a representative: no chains), different (a hash collision)
-//      -> i represents itself, so the method is exact whatever the hash does.  Per-block counts of the non-flat and
-//      the flat representatives and of the call's non-flat tiles.
-//   ft_flat_scan_kernel over the three rows of counts, then C (ft_dedup_place_kernel): stable positions of the
-//      representatives, non-flat first, flat after, each in tile order (no atomics: the layout is deterministic).
-//   D (ft_dedup_scatter_kernel): every tile takes the outputs at its representative's position.
-// 16 lanes per tile (one int4 each: a wave reads 1 KiB contiguous), 16 tiles per group, 256 tiles per workgroup.
-static constexpr unsigned long long FT_DD_EMPTY = ~0ull;
-
-__device__ __forceinline__ unsigned long long ft_dd_mix(unsigned long long x) {  // splitmix64's finaliser
-    x ^= x >> 30;
-    x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27;
-    x *= 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    return x;
-}
-
-// the 16 ballot bits of this lane's group of 16
-__device__ __forceinline__ unsigned ft_dd_group_bits(unsigned long long b) {
-    return (unsigned)(b >> (threadIdx.x & 48)) & 0xffffu;
-}
-
-__global__ __launch_bounds__(256) void ft_dedup_hash_kernel(const int32_t *__restrict__ rgb, int Q,
-                                                            unsigned long long kmask, unsigned long long *tkey,
-                                                            unsigned int *tmin, unsigned int tmask, uint8_t *flag,
-                                                            int *slot) {
-    const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
-    const long base = (long)blockIdx.x * 256;
-    for (int it = 0; it < 16; it++) {
-        const long i = base + it * 16 + g;  // uniform over the group of 16
-        const bool in = i < Q;
-        int4 v = make_int4(0, 0, 0, 0);
-        if (in) v = reinterpret_cast<const int4 *>(rgb)[i * 16 + l];
-        const int c0 = __shfl(v.x, 0, 16);
-        const bool flat = ft_dd_group_bits(__ballot(v.x == c0 && v.y == c0 && v.z == c0 && v.w == c0)) == 0xffffu;
-        const unsigned long long a = ((unsigned long long)(unsigned)v.x << 32) | (unsigned)v.y;
-        const unsigned long long b = ((unsigned long long)(unsigned)v.z << 32) | (unsigned)v.w;
-        // position-salted terms, summed over the 16 lanes
-        unsigned long long h = ft_dd_mix(a + 0x9E3779B97F4A7C15ull * (unsigned)(2 * l + 1)) +
-                               ft_dd_mix(b + 0x9E3779B97F4A7C15ull * (unsigned)(2 * l + 2));
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) h += __shfl_xor(h, o, 16);
-        if (l != 0 || !in) continue;
-        unsigned long long key = ft_dd_mix(h) & kmask;
-        if (key == FT_DD_EMPTY) key = 0;
-        unsigned int s = (unsigned int)(key ^ (key >> 32)) & tmask;
-        for (;;) {  // at most Q keys in >= 2 Q slots: an empty slot or the key's own is always met
-            unsigned long long cur = __atomic_load_n(&tkey[s], __ATOMIC_RELAXED);  // (a stale EMPTY is settled by the CAS; a key never changes once set)
-            if (cur == FT_DD_EMPTY) {
-                cur = atomicCAS(&tkey[s], FT_DD_EMPTY, key);
-                if (cur == FT_DD_EMPTY) cur = key;
-            }
-            if (cur == key) break;
-            s = (s + 1) & tmask;
-        }
-        atomicMin(&tmin[s], (unsigned int)i);
-        slot[i] = (int)s;
-        flag[i] = flat ? 1 : 0;
-    }
-}
-
-__global__ __launch_bounds__(256) void ft_dedup_rep_kernel(const int32_t *__restrict__ rgb, int Q,
-                                                           const unsigned int *__restrict__ tmin,
-                                                           const int *__restrict__ slot,
-                                                           const uint8_t *__restrict__ flag, int *rep_of, int *bcnt,
-                                                           int nb) {
-    __shared__ int cnt[3];
-    if (threadIdx.x < 3) cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
-    const long base = (long)blockIdx.x * 256;
-    int c_nf = 0, c_fl = 0, c_all = 0;
-    for (int it = 0; it < 16; it++) {
-        const long i = base + it * 16 + g;
-        const bool in = i < Q;
-        const long r = in ? (long)tmin[slot[i]] : 0;  // <= i: tile i itself took part in the minimum
-        const bool cmp = in && r != i;
-        bool eq = true;
-        if (cmp) {
-            const int4 a = reinterpret_cast<const int4 *>(rgb)[i * 16 + l];
-            const int4 b = reinterpret_cast<const int4 *>(rgb)[r * 16 + l];
-            eq = a.x == b.x && a.y == b.y && a.z == b.z && a.w == b.w;
-        }
-        const bool same = ft_dd_group_bits(__ballot(eq)) == 0xffffu;
-        if (l != 0 || !in) continue;
-        const bool dup = cmp && same;
-        rep_of[i] = dup ? (int)r : (int)i;
-        const int f = flag[i];
-        c_all += f ? 0 : 1;
-        if (!dup) {
-            c_nf += f ? 0 : 1;
-            c_fl += f ? 1 : 0;
-        }
-    }
-    if (l == 0) {
-        atomicAdd(&cnt[0], c_nf);
-        atomicAdd(&cnt[1], c_fl);
-        atomicAdd(&cnt[2], c_all);
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) bcnt[(size_t)threadIdx.x * nb + blockIdx.x] = cnt[threadIdx.x];
-}
-
-// boff: the scanned counts [3][nb]; total [0]: non-flat representatives
-__global__ __launch_bounds__(256) void ft_dedup_place_kernel(int Q, const uint8_t *__restrict__ flag,
-                                                             const int *__restrict__ rep_of,
-                                                             const int *__restrict__ boff, int nb,
-                                                             const int *__restrict__ total, int *perm, int *slot_of) {
-    __shared__ int sc[256];
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    const bool rep = i < Q && rep_of[i] == (int)i;
-    const int f = rep ? flag[i] : 0;
-    const int mine = rep ? (f ? 1 << 16 : 1) : 0;  // low half: non-flat representatives, high half: flat ones
-    sc[threadIdx.x] = mine;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-        const int u = threadIdx.x >= o ? sc[threadIdx.x - o] : 0;
-        __syncthreads();
-        sc[threadIdx.x] += u;
-        __syncthreads();
-    }
-    if (!rep) return;
-    const int before = sc[threadIdx.x] - mine;
-    const long pos = f ? (long)*total + boff[(size_t)nb + blockIdx.x] + (before >> 16)
-                       : (long)boff[blockIdx.x] + (before & 0xffff);
-    perm[pos] = (int)i;
-    slot_of[i] = (int)pos;
-}
-
-__global__ __launch_bounds__(256) void ft_dedup_scatter_kernel(int Q, const int *__restrict__ rep_of,
-                                                               const int *__restrict__ slot_of, const int *fidx,
-                                                               const float *ferr, const int32_t *ftile,
-                                                               const int32_t *fpal, const uint8_t *fhm,
-                                                               const uint8_t *fvm, int *idx, float *err, FtMaps maps) {
-    const long o = (long)blockIdx.x * 256 + threadIdx.x;
-    if (o >= Q) return;
-    const long p = slot_of[rep_of[o]];
-    if (idx) idx[o] = fidx[p];
-    if (err) err[o] = ferr[p];
-    if (maps.tile) maps.tile[o] = ftile[p];
-    if (maps.pal) maps.pal[o] = fpal[p];
-    if (maps.hm) maps.hm[o] = fhm[p];
-    if (maps.vm) maps.vm[o] = fvm[p];
-}
-
-static std::atomic<int> g_ft_dedup{1};  // tiler_debug_ft_dedup
-void nn_set_ft_dedup(int mode) { g_ft_dedup.store(mode); }
-
-int nn_frame_tiling_dev(NNIndex *ix, const int32_t *d_rgb, int Q, int use_wavelets, int gamma, int *d_idx,
-                        float *d_err, const FtMaps *maps, hipStream_t stream) {
-    if (Q <= 0) return 0;
-    if (ix->d != 192) {
-        set_error("frame tiling: dataset dimension must be 192 (cTileDCTSize)");
-        return -1;
-    }
-    SearchScratch &s = ix->scratch;
-    if ((size_t)Q > s.cap_rows) {
-        if (s.qrows) (void)hipDeviceSynchronize();  // the outgrown buffer goes back to the block cache (ensure_scratch)
-        dfree(s.qrows);
-        s.qrows = nullptr;
-        s.cap_rows = 0;
-        TILER_HIP_CHECK(dmalloc((void **)&s.qrows, (size_t)Q * 192 * sizeof(float)));
-        s.cap_rows = Q;
-    }
-    const bool fuse_rb = ix->kd && use_wavelets && ix->kd->dd == 192;
-    if (fuse_rb && ensure_scratch(ix, Q, 0)) return -1;
-    constexpr bool noflat = false;
-    // flat grouping on the generic path (datasets without mirror orbits: real PrepareFrameTiling candidate sets):
-    // the 16x16x32 shortlist's flat workgroups contract k-step 0 only (dc_first_dim)
-    const bool flat_generic = !ix->orbit && use_wavelets && ix->S16 > 0 && shortlist16_L() > 0 && Q >= 8192;
-    // flat tiles last (see ft_flat_flag_kernel) when the shortlist is long enough to repay the ~0.1 ms of grouping: C3
-    // (2,048 group blocks) -0.6..-1.1 ms per step; C2 (512 blocks, whose ragged last round the mixed split already
-    // fills) +0.08 ms (profiles/flat_c2_ab.sh), so not there
-    const bool group = !noflat && Q >= 8192 &&
-                       (flat_generic || (ix->orbit && use_wavelets && ((const OrbitIndex *)ix->orbit)->gblk >= 1024));
-    // each distinct tile searched once (see ft_dedup_hash_kernel); the query kernels read through a permutation on
-    // the Haar path only
-    const int dd_mode = g_ft_dedup.load(std::memory_order_relaxed);
-    const bool dedup = dd_mode != 0 && use_wavelets && Q >= 8192;
-    if (group || dedup) {
-        const int nb = (Q + 255) / 256;
-        if ((size_t)Q > s.cap_flat) {
-            if (s.fperm || s.fbcnt || s.fflag || s.fidx || s.ferr || s.ftile || s.fpal || s.fhm || s.fvm || s.dslot ||
-                s.drep || s.dpos)
-                (void)hipDeviceSynchronize();  // (as above)
-            dfree(s.fperm);
-            dfree(s.fbcnt);
-            dfree(s.fflag);
-            dfree(s.fidx);
-            dfree(s.ferr);
-            dfree(s.ftile);
-            dfree(s.fpal);
-            dfree(s.fhm);
-            dfree(s.fvm);
-            dfree(s.dslot);
-            dfree(s.drep);
-            dfree(s.dpos);
-            s.fperm = s.fbcnt = s.fidx = nullptr;  // a failed allocation below leaves nothing dangling
-            s.fflag = s.fhm = s.fvm = nullptr;
-            s.ferr = nullptr;
-            s.ftile = s.fpal = nullptr;
-            s.dslot = s.drep = s.dpos = nullptr;
-            s.cap_flat = 0;
-            if (!s.fcnt) TILER_HIP_CHECK(dmalloc((void **)&s.fcnt, 4 * sizeof(int)));
-            TILER_HIP_CHECK(dmalloc((void **)&s.fperm, (size_t)Q * sizeof(int)));
-            TILER_HIP_CHECK(dmalloc((void **)&s.fbcnt, (size_t)3 * nb * sizeof(int)));
-            TILER_HIP_CHECK(dmalloc((void **)&s.fflag, (size_t)Q));
-            TILER_HIP_CHECK(dmalloc((void **)&s.fidx, (size_t)Q * sizeof(int)));
-            TILER_HIP_CHECK(dmalloc((void **)&s.ferr, (size_t)Q * sizeof(float)));
-            TILER_HIP_CHECK(dmalloc((void **)&s.ftile, (size_t)Q * sizeof(int32_t)));
-            TILER_HIP_CHECK(dmalloc((void **)&s.fpal, (size_t)Q * sizeof(int32_t)));
-            TILER_HIP_CHECK(dmalloc((void **)&s.fhm, (size_t)Q));
-            TILER_HIP_CHECK(dmalloc((void **)&s.fvm, (size_t)Q));
-            TILER_HIP_CHECK(dmalloc((void **)&s.dslot, (size_t)Q * sizeof(int)));
-            TILER_HIP_CHECK(dmalloc((void **)&s.drep, (size_t)Q * sizeof(int)));
-            TILER_HIP_CHECK(dmalloc((void **)&s.dpos, (size_t)Q * sizeof(int)));
-            s.cap_flat = Q;
-        }
-        int nq = Q;              // queries searched
-        bool engaged = false;    // the searched batch is the representatives
-        const int *cnt = s.fcnt; // device count of the searched batch's non-flat queries
-        if (dedup) {
-            size_t slots = 1;
-            while (slots < 2 * (size_t)Q) slots <<= 1;
-            if (slots > s.cap_tab) {
-                if (s.dkey || s.dmin) (void)hipDeviceSynchronize();  // (as above)
-                dfree(s.dkey);
-                dfree(s.dmin);
-                s.dkey = nullptr;
-                s.dmin = nullptr;
-                s.cap_tab = 0;
-                TILER_HIP_CHECK(dmalloc((void **)&s.dkey, slots * sizeof(unsigned long long)));
-                TILER_HIP_CHECK(dmalloc((void **)&s.dmin, slots * sizeof(unsigned int)));
-                s.cap_tab = slots;
-            }
-            if (!ix->h_ft_cnt && !(ix->h_ft_cnt = pinned_slot())) {
-                set_error("frame tiling: pinned host allocation failed");
-                return -1;
-            }
-            {
-                KTimer tm("ft_dedup", stream);
-                TILER_HIP_CHECK(hipMemsetAsync(s.dkey, 0xff, slots * sizeof(unsigned long long), stream));
-                TILER_HIP_CHECK(hipMemsetAsync(s.dmin, 0xff, slots * sizeof(unsigned int), stream));
-                hipLaunchKernelGGL(ft_dedup_hash_kernel, dim3(nb), dim3(256), 0, stream, d_rgb, Q,
-                                   dd_mode == 2 ? 15ull : ~0ull, s.dkey, s.dmin, (unsigned int)(slots - 1), s.fflag,
-                                   s.dslot);
-                hipLaunchKernelGGL(ft_dedup_rep_kernel, dim3(nb), dim3(256), 0, stream, d_rgb, Q,
-                                   (const unsigned int *)s.dmin, (const int *)s.dslot, (const uint8_t *)s.fflag, s.drep,
-                                   s.fbcnt, nb);
-                hipLaunchKernelGGL(ft_flat_scan_kernel, dim3(3), dim3(1024), 0, stream, s.fbcnt, nb, s.fcnt);
-                TILER_HIP_CHECK(hipGetLastError());
-                TILER_HIP_CHECK(hipMemcpyAsync(ix->h_ft_cnt, s.fcnt, 3 * sizeof(int), hipMemcpyDeviceToHost, stream));
-                // placed while the counts travel (wasted only on a batch without repeats)
-                hipLaunchKernelGGL(ft_dedup_place_kernel, dim3(nb), dim3(256), 0, stream, Q, (const uint8_t *)s.fflag,
-                                   (const int *)s.drep, (const int *)s.fbcnt, nb, (const int *)s.fcnt, s.fperm, s.dpos);
-                TILER_HIP_CHECK(hipGetLastError());
-            }
-            TILER_HIP_CHECK(hipStreamSynchronize(stream));  // this stream only: the launches below are sized by U
-            const int U = ix->h_ft_cnt[0] + ix->h_ft_cnt[1];
-            if (U < 1 || U > Q) {
-                set_error("frame tiling: inconsistent representative count");
-                return -1;
-            }
-            engaged = U <= Q - Q / 8;
-            if (engaged) {
-                nq = U;
-            } else if (group) {  // few repeats: today's grouping of all Q tiles, from the flags and counts above
-                cnt = s.fcnt + 2;
-                hipLaunchKernelGGL(ft_flat_place_kernel, dim3(nb), dim3(256), 0, stream, d_rgb, Q,
-                                   (const uint8_t *)s.fflag, (const int *)(s.fbcnt + (size_t)2 * nb), cnt, s.fperm);
-                TILER_HIP_CHECK(hipGetLastError());
-            }
-        } else {
-            hipLaunchKernelGGL(ft_flat_flag_kernel, dim3(nb), dim3(256), 0, stream, d_rgb, Q, s.fflag, s.fbcnt);
-            hipLaunchKernelGGL(ft_flat_scan_kernel, dim3(1), dim3(1024), 0, stream, s.fbcnt, nb, s.fcnt);
-            hipLaunchKernelGGL(ft_flat_place_kernel, dim3(nb), dim3(256), 0, stream, d_rgb, Q, (const uint8_t *)s.fflag,
-                               (const int *)s.fbcnt, (const int *)s.fcnt, s.fperm);
-            TILER_HIP_CHECK(hipGetLastError());
-        }
-        if (engaged || group) {
-            FtMaps fm;
-            if (maps) fm = FtMaps{s.ftile, s.fpal, s.fhm, s.fvm};
-            // the shortlist reads the non-flat count on the device (no host sync)
-            ix->flat_cnt = group ? cnt : nullptr;
-            int rc = 0;
-            if (!(ix->orbit && use_wavelets)) {
-                PsyvArgs pa;
-                pa.n = nq;
-                pa.rgb = d_rgb;
-                pa.perm = s.fperm;
-                pa.flags = PSYV_WAVELETS;
-                pa.gamma = gamma;
-                pa.out32 = s.qrows;
-                if (fuse_rb) {
-                    pa.box = ix->kd->d_box;
-                    pa.rootbox = s.kd_rootbox;
-                }
-                rc = launch_psyv(pa, stream);
-                if (!rc) rc = nn_search_dev(ix, s.qrows, nq, 1, s.fidx, s.ferr, maps ? &fm : nullptr, stream, fuse_rb);
-            } else {
-                rc = orbit_ft_queries(ix, d_rgb, nq, gamma, s.qrows, fuse_rb ? ix->kd->d_box : nullptr,
-                                      fuse_rb ? s.kd_rootbox : nullptr, stream, s.fperm);
-                if (!rc)
-                    rc = nn_search_dev(ix, s.qrows, nq, 1, s.fidx, s.ferr, maps ? &fm : nullptr, stream, fuse_rb, true);
-            }
-            ix->flat_cnt = nullptr;
-            if (rc) return -1;
-            if (engaged) {
-                ix->last_queries = Q;
-                ix->last_dup = Q - nq;
-                ix->last_ft_nonflat = ix->h_ft_cnt[2];
-                KTimer tm("ft_dedup", stream);
-                hipLaunchKernelGGL(ft_dedup_scatter_kernel, dim3(nb), dim3(256), 0, stream, Q, (const int *)s.drep,
-                                   (const int *)s.dpos, (const int *)s.fidx, (const float *)s.ferr,
-                                   (const int32_t *)s.ftile, (const int32_t *)s.fpal, (const uint8_t *)s.fhm,
-                                   (const uint8_t *)s.fvm, d_idx, d_err, maps ? *maps : FtMaps{});
-            } else {
-                hipLaunchKernelGGL(ft_unpermute_kernel, dim3(nb), dim3(256), 0, stream, Q, (const int *)s.fperm,
-                                   (const int *)s.fidx, (const float *)s.ferr, (const int32_t *)s.ftile,
-                                   (const int32_t *)s.fpal, (const uint8_t *)s.fhm, (const uint8_t *)s.fvm, d_idx, d_err,
-                                   maps ? *maps : FtMaps{});
-            }
-            TILER_HIP_CHECK(hipGetLastError());
-            return 0;
-        }
-    }
-    if (ix->orbit && use_wavelets) {
-        // one kernel: descriptors + the orbit search's q' fragments and statistics (+ the kd root box)
-        if (orbit_ft_queries(ix, d_rgb, Q, gamma, s.qrows, fuse_rb ? ix->kd->d_box : nullptr,
-                             fuse_rb ? s.kd_rootbox : nullptr, stream))
-            return -1;
-        return nn_search_dev(ix, s.qrows, Q, 1, d_idx, d_err, maps, stream, fuse_rb, true);
-    }
-    PsyvArgs pa;
-    pa.n = Q;
-    pa.rgb = d_rgb;
-    pa.flags = use_wavelets ? PSYV_WAVELETS : 0;
-    pa.gamma = gamma;
-    pa.out32 = s.qrows;
-    if (fuse_rb) {  // annBoxDistance of each query descriptor, in the descriptor kernel (kd pruning check)
-        pa.box = ix->kd->d_box;
-        pa.rootbox = s.kd_rootbox;
-    }
-    if (launch_psyv(pa, stream)) return -1;
-    return nn_search_dev(ix, s.qrows, Q, 1, d_idx, d_err, maps, stream, fuse_rb);
 }
 
 }  // namespace tiler

@@ -3,6 +3,7 @@
 #include <mutex>
 #include <vector>
 
+#include "frame_tiling.hpp"
 #include "kdtree.hpp"
 #include "tiler_common.hpp"
 
@@ -37,7 +38,6 @@ struct SearchScratch {
     int *idx = nullptr;
     int *fb_list = nullptr;
     int *fb_count = nullptr;  // [2]: count, pad
-    float *qrows = nullptr;   // fp32 query rows (frame-tiling path: descriptors)
     void *qfrag16 = nullptr;  // query fragments, 16-row layout
     float *thr = nullptr;     // tier-2 thresholds [nq]
     float2 *gate = nullptr;   // [nq] the generic k = 1 shortlist's insertion gate: T(kk) = (kk + x) * b + y (gate16_kernel)
@@ -49,22 +49,21 @@ struct SearchScratch {
     int *kd_count = nullptr;  // [1]
     float *kd_rootbox = nullptr;  // [nq] annBoxDistance of each query to the kd-tree's enclosing box
     uint8_t *kd_done = nullptr;   // [nq] 1: the pair pass already checked this query's winner
-    // FrameTiling: flat tiles moved last (their descriptors have only isotypic block 0)
-    // fperm [Q]: new -> original; fbcnt [3][blocks]: per-block counts (non-flat representatives, flat representatives,
-    // the call's non-flat tiles; without dedupe only the first row, the non-flat tiles); fcnt [4]: their totals
-    int *fperm = nullptr, *fbcnt = nullptr, *fcnt = nullptr;
-    uint8_t *fflag = nullptr;
-    int *fidx = nullptr;
-    float *ferr = nullptr;
-    int32_t *ftile = nullptr, *fpal = nullptr;
-    uint8_t *fhm = nullptr, *fvm = nullptr;
-    // FrameTiling: each distinct tile of a call searched once (ft_dedup_* kernels).  dkey / dmin [cap_tab]: the call's
-    // hash table (key, smallest tile index of the key); dslot [Q]: a tile's table slot; drep [Q]: the tile whose
-    // result a tile takes (itself: a representative); dpos [Q]: a representative's position in the searched batch
-    unsigned long long *dkey = nullptr;
-    unsigned int *dmin = nullptr;
-    int *dslot = nullptr, *drep = nullptr, *dpos = nullptr;
-    size_t cap_q = 0, cap_keys = 0, cap_rows = 0, cap_flat = 0, cap_tab = 0;
+    size_t cap_q = 0, cap_keys = 0;
+};
+
+// The last search on an index, for tiler_search_stats (reset by every nn_search_dev).
+struct LastSearch {
+    long long queries = 0, fallback = 0;
+    int splits = 0;
+    // flat_queries: queries in all-flat shortlist workgroups, computed when the stats are read from the device count
+    // (flat_dev) and the launch shape; 0 when the search had no flat grouping
+    const int *flat_dev = nullptr;
+    long flat_nq = 0, flat_qpw = 0, flat_wgs = 0;
+    // a FrameTiling call that searched its distinct tiles only (nn_frame_tiling_dev): queries is the call's Q, searched
+    // the representatives, dup = Q - searched, ft_nonflat the call's non-flat tiles (duplicates included; -1: no such
+    // call) from which flat_queries is reported in the call's own units
+    long long searched = 0, dup = 0, ft_nonflat = -1;
 };
 
 struct NNIndex {
@@ -73,7 +72,6 @@ struct NNIndex {
     double maxN = 0, maxH = 0, maxE = 0, max_abs = 0;
     bool exact_int = false;
     int perm = 0;               // 1: candidate rows spread over accumulator lanes (row_perm), float data
-    const int *flat_cnt = nullptr; // FrameTiling call in progress: device count of non-flat queries (flat ones last)
     float *d_rows = nullptr;    // [n][d] fp32 (exact rescoring)
     float *d_rowsT = nullptr;   // [ceil(n/64)][d/4][64] float4 row-interleaved copy (k = 1 small-batch scan, built on
                                 // first use; null on mirror-orbit indexes, which scan their base rows)
@@ -88,17 +86,8 @@ struct NNIndex {
     uint8_t *d_tr_attr = nullptr;
     SearchScratch scratch;
     std::mutex mu;
-    long long last_queries = 0, last_fallback = 0;
-    int last_splits = 0;
-    // flat_queries of the last search (tiler_search_stats): queries in all-flat shortlist workgroups, computed when the
-    // stats are read from the device count (last_flat_dev) and the launch shape; 0 when the search had no flat grouping
-    const int *last_flat_dev = nullptr;
-    long last_flat_nq = 0, last_flat_qpw = 0, last_flat_wgs = 0;
-    // a FrameTiling call that searched its distinct tiles only (nn_frame_tiling_dev): last_queries is the call's Q,
-    // last_searched the representatives, last_dup = Q - last_searched, last_ft_nonflat the call's non-flat tiles
-    // (duplicates included; -1: no such call) from which flat_queries is reported in the call's own units
-    long long last_searched = 0, last_dup = 0, last_ft_nonflat = -1;
-    int *h_ft_cnt = nullptr;    // pinned [4]: the dedupe counts read back inside the call
+    LastSearch last;            // what the last search did (tiler_search_stats)
+    FtScratch ft;               // FrameTiling's batch stage (frame_tiling.hip)
     hipEvent_t done_event = nullptr;  // recorded at the end of every search on its stream (stats wait on it)
     int last_orbit = 0;         // 1: the last search ran the mirror-orbit path
     OrbitIndex *orbit = nullptr; // mirror-orbit index (orbit.hip), null when not applicable
@@ -122,24 +111,29 @@ struct FtMaps {
     uint8_t *hm = nullptr, *vm = nullptr;
 };
 
+struct SearchOpts {
+    bool rootbox_ready = false;     // kd_rootbox already holds this call's box distances (fused descriptor kernel)
+    bool orbit_prepared = false;    // orbit_ft_queries already wrote this call's q' fragments and statistics
+    const int *flat_cnt = nullptr;  // device count of the non-flat queries of a batch whose flat tiles come last
+    // host-visible, fine-grained pinned memory, or null: a small-batch scan (nn_search_is_small) also writes its final
+    // results there from the device, so the caller needs no copy back; any other search leaves them
+    int *h_idx = nullptr;
+    float *h_err = nullptr;
+};
+
 // k nearest neighbours of nq fp32 query rows in HBM; results [nq][k] in HBM; async on stream.
 // If maps is non-null (k == 1) the FrameTiling tilemap items are written too.
-// h_idx / h_err (host-visible, fine-grained pinned memory, or null): a small-batch scan (nn_search_is_small) also
-// writes its final results there from the device, so the caller needs no copy back; any other search leaves them.
 int nn_search_dev(NNIndex *ix, const float *d_q, int nq, int k, int *d_idx, float *d_err, const FtMaps *maps,
-                  hipStream_t stream, bool rootbox_ready = false, bool orbit_prepared = false, int *h_idx = nullptr,
-                  float *h_err = nullptr);
+                  hipStream_t stream, const SearchOpts &opt = SearchOpts());
+// what frame_tiling.hip needs of the search: the kd root-box scratch (scratch.kd_rootbox) holds nq queries ...
+int nn_ensure_rootbox(NNIndex *ix, int nq);
+// ... and whether the index's generic shortlist runs all-flat workgroups on k-step 0 only (SearchOpts::flat_cnt)
+bool nn_generic_takes_flat(const NNIndex *ix);
 
 // batches of at most max_k1 queries (k = 1) / max_k8 (k <= 8) take the exhaustive small-batch scan; 0 disables it
 void nn_set_scan_limits(int max_k1, int max_k8);
 // test hook: every kd pruning check lists its query for the exact replay (results unchanged)
 void nn_set_force_replay(int on);
 void nn_set_shortlist_gate(int on);
-// tiler_debug_ft_dedup: 1 (default) distinct tiles of a FrameTiling call searched once, 0 off, 2 on with a 4-bit hash
-void nn_set_ft_dedup(int mode);
-
-// frame tiling: RGB tiles -> descriptors (fp32) -> search -> tilemap items
-int nn_frame_tiling_dev(NNIndex *ix, const int32_t *d_rgb, int Q, int use_wavelets, int gamma, int *d_idx,
-                        float *d_err, const FtMaps *maps, hipStream_t stream);
 
 }  // namespace tiler

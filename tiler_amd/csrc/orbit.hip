@@ -2385,20 +2385,11 @@ static constexpr int ORB_L = 4, ORB_CB = 4, ORB_NW = 8, ORB_QB = 2;
 int orbit_ensure_queries(OrbitIndex *o, int nq) {
     if ((size_t)nq <= o->cap_q) return 0;
     const long nqblk = (nq + 31) / 32;
-    if (o->qfrag || o->qstat || o->pair_cnt || o->pair_cand)  // (a first call has nothing to file: ensure_scratch)
-        (void)hipDeviceSynchronize();  // the smaller buffers go back to the block cache: earlier searches must be done
-    dfree(o->qfrag);
-    dfree(o->qstat);
-    dfree(o->pair_cnt);
-    dfree(o->pair_cand);
-    o->qfrag = nullptr;  // a failed allocation below leaves nothing dangling
-    o->qstat = nullptr;
-    o->pair_cnt = o->pair_cand = nullptr;
     o->cap_q = 0;
-    TILER_HIP_CHECK(dmalloc((void **)&o->pair_cnt, (size_t)nq * sizeof(int)));
-    TILER_HIP_CHECK(dmalloc((void **)&o->pair_cand, (size_t)nq * ORB_PSLOTS * sizeof(int)));
-    TILER_HIP_CHECK(dmalloc(&o->qfrag, (size_t)(nqblk + 1) * OS * 1024));
-    TILER_HIP_CHECK(dmalloc((void **)&o->qstat, (size_t)nq * sizeof(OrbitStat)));
+    TILER_HIP_CHECK(dregrow({{o->pair_cnt, (size_t)nq * sizeof(int)},
+                             {o->pair_cand, (size_t)nq * ORB_PSLOTS * sizeof(int)},
+                             {o->qfrag, (size_t)(nqblk + 1) * OS * 1024},
+                             {o->qstat, (size_t)nq * sizeof(OrbitStat)}}));
     o->cap_q = nq;
     return 0;
 }
@@ -2472,14 +2463,8 @@ int orbit_search(NNIndex *ix, const float *d_q, int nq, const OrbitTail &tail, h
     if (orbit_ensure_queries(o, nq)) return -1;
     const size_t nkeys = (size_t)nq * nsplit * 2 * ORB_L;
     if (nkeys > o->cap_keys) {
-        if (o->key || o->id) (void)hipDeviceSynchronize();  // (as orbit_ensure_queries)
-        dfree(o->key);
-        dfree(o->id);
-        o->key = nullptr;
-        o->id = nullptr;
         o->cap_keys = 0;
-        TILER_HIP_CHECK(dmalloc((void **)&o->key, nkeys * sizeof(float)));
-        TILER_HIP_CHECK(dmalloc((void **)&o->id, nkeys * sizeof(int)));
+        TILER_HIP_CHECK(dregrow({{o->key, nkeys * sizeof(float)}, {o->id, nkeys * sizeof(int)}}));
         o->cap_keys = nkeys;
     }
     if (!queries_prepared) {  // (the FrameTiling path prepares them inside its descriptor kernel, orbit_ft_queries)
@@ -2612,11 +2597,11 @@ int orbit_search(NNIndex *ix, const float *d_q, int nq, const OrbitTail &tail, h
         o->last_expansions = h[0];
         o->last_rescored = h[1];
     }
-    ix->last_splits = nsplit;
-    ix->last_flat_dev = flat_cnt;  // flat_queries: derived from the device count when the stats are read
-    ix->last_flat_nq = nq;
-    ix->last_flat_qpw = qpw_q;
-    ix->last_flat_wgs = wgs;
+    ix->last.splits = nsplit;
+    ix->last.flat_dev = flat_cnt;  // flat_queries: derived from the device count when the stats are read
+    ix->last.flat_nq = nq;
+    ix->last.flat_qpw = qpw_q;
+    ix->last.flat_wgs = wgs;
     return 0;
 }
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
 #include <string>
 
 namespace tiler {
@@ -33,6 +34,18 @@ const Luts &luts();
 hipError_t dmalloc(void **p, size_t bytes);
 void dfree(void *p);
 void dfree_sync(void *p);
+// One buffer of a group that grows together: where its pointer lives and its new size.
+struct DevBuf {
+    template <class T>
+    DevBuf(T *&ptr, size_t bytes) : p((void **)&ptr), bytes(bytes) {}
+    void **p;
+    size_t bytes;
+};
+// Replace a group of buffers: if any is held, one hipDeviceSynchronize() (dfree's rule: the outgrown blocks go back to
+// the cache, so earlier work must be done; a group's first call holds nothing and waits for nothing), then every one
+// freed and nulled, then (alloc) every one allocated anew.  On an error nothing of the group stays allocated.
+// alloc = false only releases; idle: the caller has already waited for the device.
+hipError_t dregrow(std::initializer_list<DevBuf> bufs, bool alloc = true, bool idle = false);
 // non-blocking streams of the current device, reused (stream_put synchronises the stream first)
 hipError_t stream_get(hipStream_t *s);
 void stream_put(hipStream_t s);

@@ -51,6 +51,11 @@ def lib():
     return _o
 
 
+def set_gamma(g0=2.0, g1=0.6):
+    """gGamma (main.pas:586, set from the form at 1443-1444): the exponents behind gamma 0 / 1; rebuilds the restatement's LUTs."""
+    lib().or_set_gamma(float(g0), float(g1))
+
+
 def psyv(rgb=None, palpix=None, pal=None, flags=0, gamma=-1):
     out = np.zeros(192, np.float64)
     rgb = None if rgb is None else np.ascontiguousarray(rgb, np.int32)

@@ -3,6 +3,9 @@
 Bar: descriptors fp64 bit-exact; distances fp32 bit-exact; tile / palette / mirror
 indices bit-exact under ANN's kd-tree tie order (the reference's, default) and under the lowest-index
 opt-in (split = TILER_SPLIT_INDEX_ORDER).
+
+FrameTiling runs here at the form's default setting (wavelets on, gamma -1); the DCT descriptor, gamma 0 / 1 and
+tiler_set_gamma are held to the same bar in test_gpu_ft_modes.py.
 """
 import numpy as np
 import pytest

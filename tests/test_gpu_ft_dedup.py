@@ -59,10 +59,9 @@ def orbit_case(gpu):
     kt.finish_frame_tiling()
 
 
-@pytest.fixture(scope="module")
-def generic_case(gpu):
-    """The two-cells-per-tile candidate set (no mirror orbits: the generic 16x16x32 shortlist) with 8 x 1,200 tiles."""
-    from tiler_amd.frame_tiling import KeyframeTiler
+def generic_inputs():
+    """The two-cells-per-tile candidate set (never a whole mirror orbit) and 8 x 1,200 frame tiles:
+    ((used, tiles, thm, tvm, pals), ds, frames)."""
     rng = np.random.default_rng(29)
     P, T = 16, 6000
     tiles, thm, tvm = synth.tileset(rng, T)
@@ -71,8 +70,16 @@ def generic_case(gpu):
     for _ in range(2):
         used[rng.integers(0, P, T), np.arange(T), rng.integers(0, 4, T)] = 1
     ds = synth.ft_dataset_from_used(used, thm, tvm)
-    kt = KeyframeTiler(tiles, thm, tvm, pals, ds)
     frames = synth.keyframe_frames(rng, 8, 1200)
+    return (used, tiles, thm, tvm, pals), ds, frames
+
+
+@pytest.fixture(scope="module")
+def generic_case(gpu):
+    """The two-cells-per-tile candidate set (no mirror orbits: the generic 16x16x32 shortlist) with 8 x 1,200 tiles."""
+    from tiler_amd.frame_tiling import KeyframeTiler
+    (used, tiles, thm, tvm, pals), ds, frames = generic_inputs()
+    kt = KeyframeTiler(tiles, thm, tvm, pals, ds)
     rows = np.ascontiguousarray(frames.reshape(-1, 64))
     off, st_off = _run(gpu, kt, rows, 0)
     yield {"kt": kt, "frames": frames, "rows": rows, "off": off, "st_off": st_off, "distinct": _distinct(rows),

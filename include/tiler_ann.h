@@ -162,7 +162,7 @@ const char *tiler_last_error(void); /* thread-local message of the last failure 
 int tiler_set_gamma(double g0, double g1); /* gGamma main.pas:586 / 1441-1447; rebuilds gGammaCorLut */
 /* Kernel timing with HIP events on the launching stream (bench/profiling): enable, then read the
  * summed milliseconds and launch count of one kernel family ("psyv", "nn_prep", "nn_shortlist",
- * "nn_rescore", "nn_exact", "smooth", "kmodes", "render", "quality", "ft_dedup": FrameTiling's duplicate-tile
+ * "nn_rescore", "nn_exact", "smooth", "kmodes", "render", "quality", "reload_match", "ft_dedup": FrameTiling's duplicate-tile
  * passes and scatter).  Reading synchronises the recorded events. */
 int tiler_timing_enable(int on);
 double tiler_timing_get(const char *kernel, int *launches);
@@ -262,6 +262,45 @@ int tiler_debug_kmodes_ff_fallback(int on);
 /* Medoids of every bin's clusters (as tiler_kmodes_medoids per bin): medoid[sum k] bin-local rows. */
 int tiler_kmodes_medoids_batch(const uint8_t *X, const int32_t *bin_off, int nbins, const int32_t *k,
                                const int32_t *labels, const uint8_t *centroids, int32_t *medoid, int32_t *counts);
+
+/* ---- GlobalTiling, reload branch (ReloadPreviousTiling main.pas:4372-4470) ----
+ * Batched GetMinMatchingDissim (kmodes.pas:598-604): rows[n][80] dataset lines of arbitrary bytes, group g = rows
+ * [grp_off[g], grp_off[g+1]); every item items[i][80] is searched in group item_grp[i], or in all n rows when that is
+ * -1, out of range or an empty group.  idx_out[i] = the row of minimal dissimilarity (2048 mismatch + W0 + W4, the
+ * asm's int8 wrap and mod-2^16 words included), ties to the LAST row; -1 (and dis ~0) when n = 0, as the asm returns.
+ * At most 1023 groups.  0 / -1. */
+int tiler_min_matching_dissim_groups(const uint8_t *rows, int64_t n, const int32_t *grp_off, int ngroups,
+                                     const uint8_t *items, const int32_t *item_grp, int64_t m, int32_t *idx_out,
+                                     uint64_t *dis_out);
+/* The same with rows / items (16-byte aligned) / item_grp / idx / dis in HBM; grp_off is a host array.  Synchronous. */
+int tiler_min_matching_dissim_groups_dev(const uint8_t *d_rows, int64_t n, const int32_t *grp_off, int ngroups,
+                                         const uint8_t *d_items, const int32_t *d_item_grp, int64_t m, int32_t *d_idx,
+                                         uint64_t *d_dis, void *stream);
+/* A saved tileset (.gts, main.pas:4359-4367) resident in HBM.  raw[n][64]: the file's tiles in file order (host);
+ * every byte becomes (v * palsize) div file_palsize kept as a byte (main.pas:4436-4438), every tile its 80-byte
+ * dataset line (WriteTileDatasetLine) bucketed by PalSigni (GetTilePalZoneThres' return value, 16 zones of the clip's
+ * palsize).  n = 0 is allowed.  NULL on error. */
+typedef struct tiler_tileset tiler_tileset;
+tiler_tileset *tiler_tileset_load(const uint8_t *raw, int64_t n, int file_palsize, int palsize);
+int tiler_tileset_destroy(tiler_tileset *ts);
+/* DoFindBest (main.pas:4377-4410) over a tile list: every tile with active[i] != 0 gets the first 64 bytes of its
+ * closest line of the tileset -- searched in the bucket of the tile's own PalSigni, in the whole set when that bucket
+ * is empty; ties to the last row -- written over palpix[i]; idx_out[i] = that line's file-order row, dis_out[i] its
+ * dissimilarity (either may be NULL).  Inactive tiles are untouched, idx -1.  With an empty tileset nothing changes
+ * and every idx is -1.  Host buffers.  0 / -1. */
+int tiler_tileset_match(tiler_tileset *ts, uint8_t *palpix, const uint8_t *active, int64_t nt, int32_t *idx_out,
+                        uint64_t *dis_out);
+/* The same with every array in HBM (palpix 16-byte aligned); queries go through in passes of bounded scratch.
+ * Synchronous. */
+int tiler_tileset_match_dev(tiler_tileset *ts, uint8_t *d_palpix, const uint8_t *d_active, int64_t nt, int32_t *d_idx,
+                            uint64_t *d_dis, void *stream);
+/* Test / study hook (process-wide): chunk > 0 = queries per pass (0: the default, 2^20); qpt = queries per thread of
+ * the argmin kernel, 1 or 2 (0: the default); slices > 0 = row slices per query block (0: chosen from the number of
+ * query blocks).  Results are identical either way.  0 / -1. */
+int tiler_debug_reload(int64_t chunk, int qpt, int slices);
+/* (query, row) dissimilarities the last tiler_tileset_match[_dev] / tiler_min_matching_dissim_groups[_dev] call of
+ * the process evaluated. */
+int tiler_reload_last_pairs(int64_t *pairs);
 
 /* ---- Load-step keyframe detection (btnLoadClick main.pas:1099-1146) ----------------
  * frames[F][tm_h*tm_w][64] int32 0x00BBGGRR (TFrame.Tiles[].RGBPixels, tile-major, as FrameTiling takes

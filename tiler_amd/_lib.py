@@ -134,6 +134,16 @@ _SIGS = {
                                         c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "tiler_frame_quality": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "tiler_frame_quality_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "tiler_min_matching_dissim_groups": (c_int, [c_void_p, ctypes.c_int64, c_void_p, c_int, c_void_p, c_void_p,
+                                                 ctypes.c_int64, c_void_p, c_void_p]),
+    "tiler_min_matching_dissim_groups_dev": (c_int, [c_void_p, ctypes.c_int64, c_void_p, c_int, c_void_p, c_void_p,
+                                                     ctypes.c_int64, c_void_p, c_void_p, c_void_p]),
+    "tiler_tileset_load": (c_void_p, [c_void_p, ctypes.c_int64, c_int, c_int]),
+    "tiler_tileset_destroy": (c_int, [c_void_p]),
+    "tiler_tileset_match": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p]),
+    "tiler_tileset_match_dev": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p]),
+    "tiler_debug_reload": (c_int, [ctypes.c_int64, c_int, c_int]),
+    "tiler_reload_last_pairs": (c_int, [P(ctypes.c_int64)]),
     "tiler_lzma_encode": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_uint32, c_int, c_void_p, c_size_t,
                                   c_void_p]),
 }

@@ -30,6 +30,7 @@
 #include "orbit.hpp"
 #include "psyv.hpp"
 #include "quality.hpp"
+#include "reload.hpp"
 #include "smooth.hpp"
 
 namespace tiler {
@@ -1604,6 +1605,67 @@ int tiler_kmodes_medoids_batch(const uint8_t *X, const int32_t *bin_off, int nbi
                                const int32_t *labels, const uint8_t *centroids, int32_t *medoid, int32_t *counts) {
     if (!ensure_init()) return -1;
     return kmodes_medoids_batch_host(X, bin_off, nbins, k, labels, centroids, medoid, counts);
+}
+
+tiler_tileset *tiler_tileset_load(const uint8_t *raw, int64_t n, int file_palsize, int palsize) {
+    if (!ensure_init()) return nullptr;
+    return reinterpret_cast<tiler_tileset *>(tileset_load(raw, (long)n, file_palsize, palsize));
+}
+
+int tiler_tileset_destroy(tiler_tileset *ts) {
+    if (!ts) return 0;
+    if (!ensure_init()) return -1;
+    Tileset *t = reinterpret_cast<Tileset *>(ts);
+    DevScope ds(tileset_device(t));
+    tileset_destroy(t);
+    return 0;
+}
+
+int tiler_tileset_match(tiler_tileset *ts, uint8_t *palpix, const uint8_t *active, int64_t nt, int32_t *idx_out,
+                        uint64_t *dis_out) {
+    if (!ensure_init()) return -1;
+    if (!ts) {
+        set_error("tileset_match: null handle");
+        return -1;
+    }
+    Tileset *t = reinterpret_cast<Tileset *>(ts);
+    DevScope ds(tileset_device(t));
+    return tileset_match_host(t, palpix, active, (long)nt, idx_out, dis_out);
+}
+
+int tiler_tileset_match_dev(tiler_tileset *ts, uint8_t *d_palpix, const uint8_t *d_active, int64_t nt, int32_t *d_idx,
+                            uint64_t *d_dis, void *stream) {
+    if (!ensure_init()) return -1;
+    if (!ts) {
+        set_error("tileset_match: null handle");
+        return -1;
+    }
+    Tileset *t = reinterpret_cast<Tileset *>(ts);
+    DevScope ds(tileset_device(t));
+    return tileset_match_dev(t, d_palpix, d_active, (long)nt, d_idx, d_dis, (hipStream_t)stream);
+}
+
+int tiler_min_matching_dissim_groups(const uint8_t *rows, int64_t n, const int32_t *grp_off, int ngroups,
+                                     const uint8_t *items, const int32_t *item_grp, int64_t m, int32_t *idx_out,
+                                     uint64_t *dis_out) {
+    if (!ensure_init()) return -1;
+    return min_dissim_groups_host(rows, (long)n, grp_off, ngroups, items, item_grp, (long)m, idx_out, dis_out);
+}
+
+int tiler_min_matching_dissim_groups_dev(const uint8_t *d_rows, int64_t n, const int32_t *grp_off, int ngroups,
+                                         const uint8_t *d_items, const int32_t *d_item_grp, int64_t m, int32_t *d_idx,
+                                         uint64_t *d_dis, void *stream) {
+    if (!ensure_init()) return -1;
+    DevScope ds(ptr_device(d_items));
+    return min_dissim_groups_dev(d_rows, (long)n, grp_off, ngroups, d_items, d_item_grp, (long)m, d_idx, d_dis,
+                                 (hipStream_t)stream);
+}
+
+int tiler_debug_reload(int64_t chunk, int qpt, int slices) { return reload_debug((long)chunk, qpt, slices); }
+
+int tiler_reload_last_pairs(int64_t *pairs) {
+    if (pairs) *pairs = reload_last_pairs();
+    return 0;
 }
 
 }  // extern "C"

@@ -142,6 +142,32 @@ class Encoder:
         self.reindex_tiles()
         return kpb
 
+    def save_tileset(self, path_or_file=None) -> bytes:
+        """The .gts file DoGlobalTiling ends with (main.pas:4357-4367): the palette size and every Active tile's
+        PalPixels in index order.  Valid after do_global_tiling; also written to a path or a binary file if given."""
+        data = gt.write_tileset(self.palpix, self.active, self.palsize)
+        if isinstance(path_or_file, (str, bytes)) or hasattr(path_or_file, "__fspath__"):
+            with open(path_or_file, "wb") as f:
+                f.write(data)
+        elif path_or_file is not None:
+            path_or_file.write(data)
+        return data
+
+    def do_reload_tiling(self, tileset):
+        """btnDoGlobalTilingClick with chkReload (main.pas:845-850) -> ReloadPreviousTiling main.pas:4372-4470, the
+        step that takes the place of do_global_tiling: every Active tile snapped to its closest tile of a saved
+        tileset (.gts bytes, a path or a binary file; matched on the GPU), then MakeTilesUnique over all tiles.  No
+        K-Modes and no ReindexTiles.  Returns the per-tile (idx, dis) of the match."""
+        if isinstance(tileset, str) or hasattr(tileset, "__fspath__"):
+            with open(tileset, "rb") as f:
+                tileset = f.read()
+        elif hasattr(tileset, "read"):
+            tileset = tileset.read()
+        with gt.Tileset(tileset, self.palsize) as ts:
+            self.palpix, idx, dis = ts.match(self.palpix, self.active)
+        self.make_tiles_unique()
+        return idx, dis
+
     def do_frame_tiling(self, quality: int = ft.FT_MEDIUM, use_wavelets: bool = True, gamma: int = -1):
         """btnDoFrameTilingClick main.pas:945-977: PrepareGlobalFT, then per keyframe PrepareFrameTiling
         (over the keyframe's current TileMap items), DoFrameTiling of all its frames, FinishFrameTiling."""
@@ -248,10 +274,14 @@ class Encoder:
         corr, sse = frame_quality(src, rgb, tm_w, tm_h)
         return {"corr": corr, "psnr": psnr(sse, tm_w, tm_h), "sse": sse, "rgb": rgb, "invalid": invalid}
 
-    def run_all(self, desired: int, quality: int = ft.FT_MEDIUM, strength: float = DEFAULT_STRENGTH):
-        """btnRunAllClick main.pas:1232-1272 from MakeUnique to Smooth."""
+    def run_all(self, desired: int, quality: int = ft.FT_MEDIUM, strength: float = DEFAULT_STRENGTH, reload=None):
+        """btnRunAllClick main.pas:1232-1272 from MakeUnique to Smooth.  reload: a saved tileset (.gts bytes, path
+        or file) -> the GlobalTiling step is do_reload_tiling(reload) instead of do_global_tiling(desired)."""
         self.do_make_unique()
-        self.do_global_tiling(desired)
+        if reload is not None:
+            self.do_reload_tiling(reload)
+        else:
+            self.do_global_tiling(desired)
         self.do_frame_tiling(quality)
         self.do_reindex()
         return self.do_smooth(strength)
@@ -269,7 +299,9 @@ class DistributedEncoder(Encoder):
     maps rows to frames).  Exchanges (fixed-layout tensors, tiler_amd.dist): the K-Modes merge map (all-reduce
     MAX) so every rank holds the reduced tileset, the UseCount histogram (all-reduce SUM) for ReindexTiles, and for
     SaveStream each rank's compressed keyframe streams onto rank `save_rank` (gather_units).  save_stream is a
-    collective: every rank calls it, save_rank gets the .gtm bytes, the others None."""
+    collective: every rank calls it, save_rank gets the .gtm bytes, the others None.
+    do_reload_tiling is inherited: every rank matches the whole, replicated tile list against the saved tileset and
+    gets the same answer; sharding the match across ranks is out of scope."""
 
     def __init__(self, v: Video, palsize: int = 16, device: int | None = None, save_rank: int = 0):
         import os

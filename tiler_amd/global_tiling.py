@@ -8,6 +8,11 @@ reference runs the bins concurrently with ProcThreadPool, main.pas:4339):
   do_global_tiling         DoGlobalTiling 4256-4331 + DoKModes 4195-4254 + MergeTiles 3688-3712
   make_tiles_unique        MakeTilesUnique 2555-2612 (stable order: lowest index represents duplicates)
   reindex_tiles            ReindexTiles 4483-4527 (UseCount desc, old index asc)
+The reload branch (ReloadPreviousTiling main.pas:4372-4470) snaps every active tile to its closest tile of a saved
+tileset instead; the matching runs on the GPU (tiler_tileset_load / tiler_tileset_match):
+  write_tileset / read_tileset  the .gts file (main.pas:4359-4367 / 4420-4438)
+  pal_signi                GetTilePalZoneThres' return value (main.pas:4142-4165)
+  reload_previous_tiling   DoFindBest 4377-4410 over all tiles + MakeTilesUnique (4464)
 """
 from __future__ import annotations
 
@@ -204,3 +209,107 @@ def reindex_tiles(active, use_count):
     idx_map = np.full(np.asarray(active).shape[0], -1, np.int64)
     idx_map[order] = np.arange(order.size)
     return idx_map
+
+
+# ---- the reload branch: .gts files and ReloadPreviousTiling (main.pas:4372-4470) ----
+def pal_signi(tiles: np.ndarray, palsize: int = 16) -> np.ndarray:
+    """[T, 64] palette indices -> [T] PalSigni, the return value of GetTilePalZoneThres with 16 zones
+    (main.pas:4142-4165): min over zones z of 64 - count(idx*16 div palsize == z), 0..64.  ReloadPreviousTiling
+    buckets by it; it is not the DitheringPalIndex DoGlobalTiling bins by."""
+    t = np.asarray(tiles, np.uint8).reshape(-1, 64)
+    zone = (t.astype(np.int64) * 16) // palsize
+    acc = np.stack([(zone == z).sum(1) for z in range(16)], 1)
+    return (64 - acc.max(1)).astype(np.int32)
+
+
+def write_tileset(palpix, active, palsize: int = 16) -> bytes:
+    """The .gts bytes DoGlobalTiling writes (main.pas:4359-4367): one byte FTilePaletteSize, then the 64 PalPixels of
+    every Active tile in tile-index order."""
+    palpix = np.asarray(palpix, np.uint8).reshape(-1, 64)
+    act = np.nonzero(np.asarray(active))[0]
+    return bytes([palsize & 255]) + np.ascontiguousarray(palpix[act]).tobytes()
+
+
+def read_tileset(data, palsize: int = 16):
+    """.gts bytes -> (rows [n][64] rescaled to the clip's palsize, the file's palette size), as ReloadPreviousTiling
+    reads them (main.pas:4420-4438): n = size div 64; a size that is no multiple of 64 starts with the file's palette
+    size, else the file is a header-less one of palette size 64; every byte becomes (v * palsize) div file_palsize,
+    kept as a byte."""
+    raw, file_palsize = _split_tileset(data)
+    if file_palsize == 0:
+        raise ValueError("read_tileset: the file's palette size is 0")
+    rows = ((raw.astype(np.int64) * palsize) // file_palsize).astype(np.uint8)
+    return rows, file_palsize
+
+
+def _split_tileset(data):
+    buf = np.frombuffer(bytes(data), np.uint8)
+    n = buf.size // 64
+    if buf.size % 64:
+        return buf[1:1 + n * 64].reshape(n, 64), int(buf[0])
+    return buf.reshape(n, 64), 64
+
+
+class Tileset:
+    """A saved tileset resident on the GPU (tiler_tileset_load): the file's tiles rescaled, as dataset lines bucketed
+    by PalSigni.  close() frees it."""
+
+    def __init__(self, data, palsize: int = 16):
+        raw, self.file_palsize = _split_tileset(data)
+        if self.file_palsize == 0:
+            raise ValueError("Tileset: the file's palette size is 0")
+        self.n, self.palsize = raw.shape[0], palsize
+        raw = np.ascontiguousarray(raw)
+        self._lib = load()
+        self._h = self._lib.tiler_tileset_load(raw.ctypes.data_as(ctypes.c_void_p), self.n, self.file_palsize, palsize)
+        if not self._h:
+            check(-1, "tiler_tileset_load")
+
+    def match(self, palpix, active):
+        """DoFindBest over all tiles: (new palpix, idx [T] file-order row or -1, dis [T])."""
+        pp = np.array(palpix, np.uint8, copy=True, order="C").reshape(-1, 64)
+        act = np.ascontiguousarray(active, np.uint8)
+        T = pp.shape[0]
+        idx = np.full(T, -1, np.int32)
+        dis = np.zeros(T, np.uint64)
+        v = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        check(self._lib.tiler_tileset_match(self._h, v(pp), v(act), T, v(idx), v(dis)), "tiler_tileset_match")
+        return pp, idx, dis
+
+    def close(self):
+        if self._h:
+            self._lib.tiler_tileset_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def min_matching_dissim_groups(rows, grp_off, items, item_grp):
+    """Batched GetMinMatchingDissim (tiler_min_matching_dissim_groups): rows [n][80] in groups [grp_off[g],
+    grp_off[g+1]), items [m][80] each searched in its group (-1 or an empty group: all rows) -> (idx [m], dis [m])."""
+    rows = np.ascontiguousarray(rows, np.uint8).reshape(-1, 80)
+    items = np.ascontiguousarray(items, np.uint8).reshape(-1, 80)
+    grp_off = np.ascontiguousarray(grp_off, np.int32)
+    item_grp = np.ascontiguousarray(item_grp, np.int32)
+    m = items.shape[0]
+    idx = np.full(m, -1, np.int32)
+    dis = np.zeros(m, np.uint64)
+    v = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    check(load().tiler_min_matching_dissim_groups(v(rows), rows.shape[0], v(grp_off), grp_off.size - 1, v(items),
+                                                  v(item_grp), m, v(idx), v(dis)), "tiler_min_matching_dissim_groups")
+    return idx, dis
+
+
+def reload_previous_tiling(palpix, active, use_count, tileset_bytes, palsize: int = 16):
+    """ReloadPreviousTiling main.pas:4372-4470: every Active tile's PalPixels become those of its closest tile of the
+    saved tileset (GPU), then MakeTilesUnique over all tiles; no K-Modes, no ReindexTiles.  Mirror flags,
+    DitheringPalIndex and the tilemaps are not touched here (the caller applies merge_index to the tilemaps).
+    Returns (palpix, active, use_count, merge_index, idx, dis); idx / dis are the per-tile match."""
+    with Tileset(tileset_bytes, palsize) as ts:
+        pp, idx, dis = ts.match(palpix, active)
+    pp, act, uc, mi = make_tiles_unique(pp, active, use_count)
+    return pp, act, uc, mi, idx, dis

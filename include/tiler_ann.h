@@ -162,8 +162,8 @@ const char *tiler_last_error(void); /* thread-local message of the last failure 
 int tiler_set_gamma(double g0, double g1); /* gGamma main.pas:586 / 1441-1447; rebuilds gGammaCorLut */
 /* Kernel timing with HIP events on the launching stream (bench/profiling): enable, then read the
  * summed milliseconds and launch count of one kernel family ("psyv", "nn_prep", "nn_shortlist",
- * "nn_rescore", "nn_exact", "smooth", "kmodes", "render", "quality", "reload_match", "ft_dedup": FrameTiling's duplicate-tile
- * passes and scatter).  Reading synchronises the recorded events. */
+ * "nn_rescore", "nn_exact", "smooth", "kmodes", "render", "quality", "reload_match", "unique_insert", "unique_last",
+ * "unique_merge", "unique_zero", "ft_dedup": FrameTiling's duplicate-tile passes and scatter).  Reading synchronises the recorded events. */
 int tiler_timing_enable(int on);
 double tiler_timing_get(const char *kernel, int *launches);
 int tiler_timing_reset(void);
@@ -301,6 +301,25 @@ int tiler_debug_reload(int64_t chunk, int qpt, int slices);
 /* (query, row) dissimilarities the last tiler_tileset_match[_dev] / tiler_min_matching_dissim_groups[_dev] call of
  * the process evaluated. */
 int tiler_reload_last_pairs(int64_t *pairs);
+
+/* ---- MakeTilesUnique (main.pas:2555-2612): the exact duplicate-tile merge ----
+ * palpix[nt][64], active[nt], use_count[nt] in and out, merge_index[nt] out.  Segment s = tiles [seg_off[s],
+ * seg_off[s+1]) (seg_off[nseg+1], a host array, non-decreasing from 0 to nt; nseg >= 1): one MakeTilesUnique per
+ * segment, as btnDoMakeUniqueClick runs one per chunk (main.pas:916-938); {0, nt} is the whole list.  Inside a
+ * segment the tiles with active != 0 and identical palpix merge into the one of lowest index (MergeTiles
+ * main.pas:3688-3712: use_count summed into it, active cleared, merge_index = its index, palpix zeroed) -- except that
+ * the segment's last tile in sorted order (the greatest 16 little-endian dwords, dword 0 first; among equals the
+ * highest index) never merges, as the reference's final DoOneMerge leaves it out (main.pas:2604-2605).  merge_index
+ * is -1 for every tile that was not merged.  The result does not depend on the order threads run in.  nt = 0 is
+ * allowed.  Host buffers.  0 / -1. */
+int tiler_make_tiles_unique(uint8_t *palpix, uint8_t *active, int64_t *use_count, int64_t *merge_index, int64_t nt,
+                            const int64_t *seg_off, int nseg);
+/* The same with the four arrays in HBM (palpix 16-byte aligned); seg_off stays a host array.  Synchronous. */
+int tiler_make_tiles_unique_dev(uint8_t *d_palpix, uint8_t *d_active, int64_t *d_use_count, int64_t *d_merge_index,
+                                int64_t nt, const int64_t *seg_off, int nseg, void *stream);
+/* Test hook (process-wide): keep only the low hash_bits bits of a tile's hash (0: every tile probes one chain of the
+ * table), -1 = the default (all bits).  Results are identical either way; for collision tests only.  0 / -1. */
+int tiler_debug_unique(int hash_bits);
 
 /* ---- Load-step keyframe detection (btnLoadClick main.pas:1099-1146) ----------------
  * frames[F][tm_h*tm_w][64] int32 0x00BBGGRR (TFrame.Tiles[].RGBPixels, tile-major, as FrameTiling takes

@@ -32,6 +32,7 @@
 #include "quality.hpp"
 #include "reload.hpp"
 #include "smooth.hpp"
+#include "unique.hpp"
 
 namespace tiler {
 
@@ -1667,5 +1668,21 @@ int tiler_reload_last_pairs(int64_t *pairs) {
     if (pairs) *pairs = reload_last_pairs();
     return 0;
 }
+
+int tiler_make_tiles_unique(uint8_t *palpix, uint8_t *active, int64_t *use_count, int64_t *merge_index, int64_t nt,
+                            const int64_t *seg_off, int nseg) {
+    if (!ensure_init()) return -1;
+    return make_tiles_unique_host(palpix, active, use_count, merge_index, (long)nt, seg_off, nseg);
+}
+
+int tiler_make_tiles_unique_dev(uint8_t *d_palpix, uint8_t *d_active, int64_t *d_use_count, int64_t *d_merge_index,
+                                int64_t nt, const int64_t *seg_off, int nseg, void *stream) {
+    if (!ensure_init()) return -1;
+    DevScope ds(ptr_device(d_palpix));
+    return make_tiles_unique_dev(d_palpix, d_active, d_use_count, d_merge_index, (long)nt, seg_off, nseg,
+                                 (hipStream_t)stream);
+}
+
+int tiler_debug_unique(int hash_bits) { return unique_debug(hash_bits); }
 
 }  // extern "C"

@@ -7,7 +7,8 @@ MakeUnique -> GlobalTiling -> FrameTiling -> Reindex -> Smooth), as host state +
   keyframes kf_start [KF+1], palettes [KF][P][16], centroids [KF][P][192]
 Each method is the reference procedure of the same name (file:line in its docstring); the heavy parts
 (K-Modes, the k=8 preselection, candidate descriptors, the FrameTiling search, Smooth) run on the GPU
-through the C ABI, the rest is the reference's host bookkeeping.  SURVEY.md 8(f)-1.
+through the C ABI, the rest is the reference's host bookkeeping -- MakeTilesUnique too unless the encoder is made
+with gpu_unique=True (tiler_make_tiles_unique; the same result).  SURVEY.md 8(f)-1.
 """
 from __future__ import annotations
 
@@ -47,9 +48,10 @@ class Encoder:
     None = all).  The tileset (palpix, flags, Active, UseCount) is always the whole clip's.  Tilemap arrays are
     [len(frames)][Q]: row r is frame frames[r]."""
 
-    def __init__(self, v: Video, palsize: int = 16, frames=None):
+    def __init__(self, v: Video, palsize: int = 16, frames=None, gpu_unique: bool = False):
         F, Q = v.frames, v.tiles_per_frame
         self.palsize = palsize
+        self.gpu_unique = bool(gpu_unique)  # MakeTilesUnique on the GPU (tiler_make_tiles_unique)
         self.n_frames = F
         self.kf_start = np.asarray(v.kf_start, np.int64)
         own = np.arange(F) if frames is None else np.asarray(frames, np.int64)
@@ -103,7 +105,8 @@ class Encoder:
         into the lowest index (TFPList.Sort is unstable, the canonical order is stable)."""
         count = self.palpix.shape[0] - first if count is None else count
         s = slice(first, first + count)
-        pp, act, uc, mi = gt.make_tiles_unique(self.palpix[s], self.active[s], self.use_count[s])
+        unique = gt.make_tiles_unique_gpu if self.gpu_unique else gt.make_tiles_unique
+        pp, act, uc, mi = unique(self.palpix[s], self.active[s], self.use_count[s])
         self.palpix[s], self.active[s], self.use_count[s] = pp, act, uc
         full = np.full(self.palpix.shape[0], -1, np.int64)
         full[s] = np.where(mi >= 0, mi + first, -1)
@@ -126,10 +129,19 @@ class Encoder:
 
     # --- steps ------------------------------------------------------------------------------------
     def do_make_unique(self):
-        """btnDoMakeUniqueClick main.pas:916-938: MakeTilesUnique per chunk of FTileMapSize * 25 tiles."""
+        """btnDoMakeUniqueClick main.pas:916-938: MakeTilesUnique per chunk of FTileMapSize * 25 tiles (gpu_unique:
+        every chunk a segment of one GPU call, then one combined merge_index applied to the tilemaps -- a chunk's
+        merges stay inside it, so this equals the per-chunk loop)."""
         chunk = self.tiles_per_frame * 25
-        for first in range(0, self.palpix.shape[0], chunk):
-            self.make_tiles_unique(first, min(chunk, self.palpix.shape[0] - first))
+        T = self.palpix.shape[0]
+        if self.gpu_unique:
+            seg_off = np.append(np.arange(0, T, chunk, dtype=np.int64), T)
+            self.palpix, self.active, self.use_count, mi = gt.make_tiles_unique_gpu(self.palpix, self.active,
+                                                                                    self.use_count, seg_off)
+            self.finish_merge_tiles(mi)
+            return
+        for first in range(0, T, chunk):
+            self.make_tiles_unique(first, min(chunk, T - first))
 
     def do_global_tiling(self, desired: int, restart: int = gt.CRANDOM_KMODES_COUNT):
         """DoGlobalTiling main.pas:4256-4370: K-Modes merge per palette bin (GPU, all bins batched),
@@ -165,7 +177,7 @@ class Encoder:
             tileset = tileset.read()
         with gt.Tileset(tileset, self.palsize) as ts:
             self.palpix, idx, dis = ts.match(self.palpix, self.active)
-        self.make_tiles_unique()
+        self.make_tiles_unique()  # (on the GPU with gpu_unique, as in do_global_tiling)
         return idx, dis
 
     def do_frame_tiling(self, quality: int = ft.FT_MEDIUM, use_wavelets: bool = True, gamma: int = -1):
@@ -303,7 +315,8 @@ class DistributedEncoder(Encoder):
     do_reload_tiling is inherited: every rank matches the whole, replicated tile list against the saved tileset and
     gets the same answer; sharding the match across ranks is out of scope."""
 
-    def __init__(self, v: Video, palsize: int = 16, device: int | None = None, save_rank: int = 0):
+    def __init__(self, v: Video, palsize: int = 16, device: int | None = None, save_rank: int = 0,
+                 gpu_unique: bool = False):
         import os
 
         import torch
@@ -323,7 +336,7 @@ class DistributedEncoder(Encoder):
         mine = sorted(self.plan[self.rank])
         own = np.concatenate([np.arange(kf_start[k], kf_start[k + 1]) for k in mine]) if mine \
             else np.zeros(0, np.int64)
-        super().__init__(v, palsize, frames=own)
+        super().__init__(v, palsize, frames=own, gpu_unique=gpu_unique)
         self.device = int(os.environ.get("LOCAL_RANK", "0")) if device is None else int(device)
         if self.device >= 0:  # device = -1: no GPU binding (host-side steps only, e.g. SaveStream in CPU tests)
             check(load().tiler_init(self.device), "tiler_init")

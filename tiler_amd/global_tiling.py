@@ -7,6 +7,7 @@ reference runs the bins concurrently with ProcThreadPool, main.pas:4339):
   equal_quality_tile_count EqualQualityTileCount main.pas:722-725
   do_global_tiling         DoGlobalTiling 4256-4331 + DoKModes 4195-4254 + MergeTiles 3688-3712
   make_tiles_unique        MakeTilesUnique 2555-2612 (stable order: lowest index represents duplicates)
+  make_tiles_unique_gpu    the same on the GPU (tiler_make_tiles_unique), any number of chunks in one call
   reindex_tiles            ReindexTiles 4483-4527 (UseCount desc, old index asc)
 The reload branch (ReloadPreviousTiling main.pas:4372-4470) snaps every active tile to its closest tile of a saved
 tileset instead; the matching runs on the GPU (tiler_tileset_load / tiler_tileset_match):
@@ -202,6 +203,26 @@ def make_tiles_unique(palpix, active, use_count):
     return palpix, active, use_count, merge_index
 
 
+def make_tiles_unique_gpu(palpix, active, use_count, seg_off=None):
+    """make_tiles_unique on the GPU (tiler_make_tiles_unique): the same (palpix, active, use_count, merge_index).
+    seg_off [nseg + 1] (non-decreasing from 0 to T): one MakeTilesUnique per segment [seg_off[s], seg_off[s+1]) in one
+    call, as btnDoMakeUniqueClick runs one per chunk; merge_index keeps whole-list indices.  None = the whole list."""
+    palpix = np.array(palpix, np.uint8, copy=True, order="C").reshape(-1, 64)
+    T = palpix.shape[0]
+    active = np.array(active, np.uint8, copy=True, order="C")
+    use_count = np.array(use_count, np.int64, copy=True, order="C")
+    if active.shape != (T,) or use_count.shape != (T,):
+        raise ValueError("make_tiles_unique_gpu: active and use_count must be [T]")
+    seg_off = np.ascontiguousarray([0, T] if seg_off is None else seg_off, np.int64).ravel()
+    if seg_off.size < 2:
+        raise ValueError("make_tiles_unique_gpu: seg_off must hold at least one segment")
+    merge_index = np.full(T, -1, np.int64)
+    v = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    check(load().tiler_make_tiles_unique(v(palpix), v(active), v(use_count), v(merge_index), T, v(seg_off),
+                                         seg_off.size - 1), "tiler_make_tiles_unique")
+    return palpix, active, use_count, merge_index
+
+
 def reindex_tiles(active, use_count):
     """ReindexTiles main.pas:4483-4527: idx_map[old] = new, order (UseCount desc, old index asc)."""
     act = np.nonzero(active)[0]
@@ -304,12 +325,13 @@ def min_matching_dissim_groups(rows, grp_off, items, item_grp):
     return idx, dis
 
 
-def reload_previous_tiling(palpix, active, use_count, tileset_bytes, palsize: int = 16):
+def reload_previous_tiling(palpix, active, use_count, tileset_bytes, palsize: int = 16, gpu_unique: bool = False):
     """ReloadPreviousTiling main.pas:4372-4470: every Active tile's PalPixels become those of its closest tile of the
-    saved tileset (GPU), then MakeTilesUnique over all tiles; no K-Modes, no ReindexTiles.  Mirror flags,
-    DitheringPalIndex and the tilemaps are not touched here (the caller applies merge_index to the tilemaps).
-    Returns (palpix, active, use_count, merge_index, idx, dis); idx / dis are the per-tile match."""
+    saved tileset (GPU), then MakeTilesUnique over all tiles (gpu_unique: on the GPU too); no K-Modes, no
+    ReindexTiles.  Mirror flags, DitheringPalIndex and the tilemaps are not touched here (the caller applies
+    merge_index to the tilemaps).  Returns (palpix, active, use_count, merge_index, idx, dis); idx / dis are the
+    per-tile match."""
     with Tileset(tileset_bytes, palsize) as ts:
         pp, idx, dis = ts.match(palpix, active)
-    pp, act, uc, mi = make_tiles_unique(pp, active, use_count)
+    pp, act, uc, mi = (make_tiles_unique_gpu if gpu_unique else make_tiles_unique)(pp, active, use_count)
     return pp, act, uc, mi, idx, dis

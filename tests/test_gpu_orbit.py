@@ -94,6 +94,44 @@ def test_orbit_not_used_for_unstructured_data(gpu, oracle):
     assert st["orbit_groups"] == 0 and st["orbit_search"] == 0
 
 
+def test_orbit_mixed_launch(gpu, oracle):
+    """The shortlist's mixed launch: one full round of n_cu workgroups scans every candidate block unsplit (part A),
+    the 44 workgroups left split the blocks (part B).  2,048 base tiles x 4 mirrors give gblk = 64 blocks, and
+    nq = (n_cu + 44) * 512 queries give n_cu + 44 workgroups.  orbit_search prices a round at its blocks + 64: the
+    best whole-batch plan is 1 split, 2 rounds x 128 = 256; the mixed plans cost 128 + (ceil(64 / ns) + 64) =
+    224, 214, 208 for ns = 2, 3, 4, each at least 2 % under the one before, so the plan is mixed with 4 splits (the
+    most the rescore takes).  Only a mixed plan reports more than 1 split here, and FrameTiling never takes it
+    (flat_cnt disables it), so this is a plain k = 1 batch search.  Samples of part A, of part B and of the last
+    workgroup are checked against ANN's kd-tree search (index, mirror flags, distance bits); a second batch 173
+    queries shorter (same plan, last workgroup and last query block partial) must repeat the first one's results."""
+    import torch
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    rng, ods, _, _, oa = _ft_rows(oracle, 37, 2048, 16)
+    nq = (n_cu + 44) * 512
+    q = gpu.psyv_batch(rgb=synth.frame_tiles(rng, nq), flags=2, want64=False, want32=True)[1]
+    with gpu.KDTree(ods) as kdt:
+        gi, ge = kdt.search_batch(q)
+        st = kdt.stats()
+        gi2, ge2 = kdt.search_batch(q[:nq - 173])
+        st2 = kdt.stats()
+    assert st["orbit_search"] == 1 and st["orbit_groups"] == 2048, st
+    assert st["splits"] == 4 and st2["splits"] == 4, (st, st2)
+    gi, gi2 = gi.reshape(-1), gi2.reshape(-1)
+    assert np.array_equal(gi2, gi[:nq - 173])
+    assert np.array_equal(ge2.view(np.uint32).reshape(-1), ge.view(np.uint32).reshape(-1)[:nq - 173])
+    a_end = n_cu * 512
+    pick = np.concatenate([rng.choice(a_end, 300, replace=False),                  # part A
+                           a_end + rng.choice(nq - a_end - 512, 300, replace=False),  # part B
+                           np.arange(nq - 512, nq)[rng.choice(512, 200, replace=False)]])  # the last workgroup
+    okd = oracle.KDTree(ods)
+    oi, oe = okd.search_batch(q[pick])
+    okd.close()
+    oi = oi.reshape(-1)
+    assert np.array_equal(gi[pick], oi), f"{np.count_nonzero(gi[pick] != oi)} of {pick.size} indices differ"
+    assert np.array_equal(np.asarray(oa)[gi[pick]] & 3, np.asarray(oa)[oi] & 3)
+    assert np.array_equal(ge.reshape(-1)[pick].view(np.uint32), oe.reshape(-1).view(np.uint32))
+
+
 def test_orbit_c2_frame_sampled(gpu, oracle):
     """C2 shape (720p frame, 16k tileset x 4 mirrors = 65,536 candidates): the whole frame through
     tiler_frame_tiling, a bounded sample checked against the exhaustive oracle scan."""

@@ -12,8 +12,8 @@
 //   * Σ (x - m_f)^2 of frame f is the SAME rounded sequence whether f is the "x" of pair (f, f+1) or the "y"
 //     of pair (f-1, f): it is computed once per frame (d2[f]);
 //   * one LANE per frame runs the ordered chains d2[f] and num[f] = Σ (x_f - m_f)(x_{f+1} - m_{f+1}), the y term
-//     coming from the neighbour lane; in the default form three producer waves compute the rounded terms into
-//     LDS and one consumer wave only adds them in order (pearson_chain_pc_kernel).
+//     coming from the neighbour lane: three producer waves compute the rounded terms into LDS and one consumer
+//     wave only adds them in order (pearson_chain_pc_kernel).
 // The chains are issue-bound fp64 work, not HBM-bound: a workgroup covers 60 frame pairs, so a launch costs about
 // one frame's worth of sequential steps whatever F is.
 // sqrt / product / division (4 flops per pair) finish on the host in double, as written in main.pas:1485-1491.
@@ -47,16 +47,11 @@ __global__ __launch_bounds__(256) void frame_sum_kernel(const int4 *__restrict__
     if ((threadIdx.x & 63) == 0 && acc) atomicAdd(&sums[f], acc);
 }
 
-// One lane per frame (60 per wave, see below) runs, in the reference's order
-// (channel-major, then screen raster: ya[i + sz*c] := FSPixels[i*3 + c], main.pas:819-826), the chains
-// d2[f] = Σ (x_f - m_f)^2 and num[f] = Σ (x_f - m_f)(x_{f+1} - m_{f+1}); every op rounded (-ffp-contract=off).
-// The y term of a pair is the NEXT lane's x term (same element, frame f+1), handed over by a DPP row shift
-// (2 v_mov_dpp; a ds_bpermute shuffle cost 30 % of the kernel), so each lane streams one frame and each element
-// costs one extract, one convert, one subtract, two moves, two multiplies and two adds (a per-lane LDS table of
-// x - m instead of convert + subtract measured 8 % slower: 189 vs 175 ms for 1,000 1080p frames).  With one wave per SIMD
-// nothing hides memory latency, so tile rows stream through a register ring KF_DEPTH rows ahead.
-constexpr int KF_FRAMES_PER_WAVE = 60;
-
+// One lane per frame runs, in the reference's order (channel-major, then screen raster: ya[i + sz*c] :=
+// FSPixels[i*3 + c], main.pas:819-826), the chains d2[f] = Σ (x_f - m_f)^2 and num[f] = Σ (x_f - m_f)(x_{f+1} -
+// m_{f+1}); every op rounded (-ffp-contract=off).  The y term of a pair is the NEXT lane's x term (same element,
+// frame f+1), handed over by a DPP row shift (2 v_mov_dpp; a ds_bpermute shuffle cost 30 % of the lane-form kernel):
+// in each row of 16 lanes, lanes 0..14 own frames and lane 15 feeds lane 14.
 // lane i <- lane i+1 of the same 16-lane row (DPP row_shl:1); lane 15 of a row gets 0 (never used)
 __device__ __forceinline__ double row_next(double v) {
     const long long b = __double_as_longlong(v);
@@ -65,91 +60,18 @@ __device__ __forceinline__ double row_next(double v) {
     return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
 }
 
-template <int KF_DEPTH, int MODE>
-__global__ __launch_bounds__(64) void pearson_chain_kernel(const int32_t *__restrict__ rgb, int F, int tm_w, int tm_h,
-                                                           const unsigned long long *__restrict__ sums,
-                                                           double *__restrict__ d2, double *__restrict__ num) {
-    const int lane = threadIdx.x;
-    // 4 rows of 16 lanes; in each row lanes 0..14 own frames and lane 15 feeds lane 14 (DPP row shifts stay
-    // inside a row), so a wave owns 60 frames
-    const int f = blockIdx.x * KF_FRAMES_PER_WAVE + 15 * (lane >> 4) + (lane & 15);
-    const int fl = f < F ? f : F - 1;  // lanes past the end replay the last frame (all lanes stay active)
-    const long fs = (long)tm_w * tm_h * 64;
-    const double m = (double)sums[fl] / (3.0 * (double)fs);
-    const int4 *a = reinterpret_cast<const int4 *>(rgb + fl * fs);
-    const int rows = tm_h * 8;
-    const long total = 3L * rows * tm_w;  // tile rows of 8 pixels, in summation order
-    int lc = 0, lsy = 0, ltx = 0;         // load cursor (channel, screen row, tile column)
-    int4 r0[KF_DEPTH], r1[KF_DEPTH];
-    int sh[KF_DEPTH];
-    auto load_next = [&](int4 &v0, int4 &v1, int &s) {
-        const long o = (((long)(lsy >> 3) * tm_w + ltx) * 64 + (lsy & 7) * 8) >> 2;
-        v0 = a[o];
-        v1 = a[o + 1];
-        s = 8 * lc;
-        if (++ltx == tm_w) {
-            ltx = 0;
-            if (++lsy == rows) {
-                lsy = 0;
-                lc = lc == 2 ? 0 : lc + 1;  // past the end: harmless re-reads, never summed
-            }
-        }
-    };
-#pragma unroll
-    for (int d = 0; d < KF_DEPTH; d++) load_next(r0[d], r1[d], sh[d]);
-    double acc_n = 0.0, acc_d = 0.0, acc_n2 = 0.0, acc_d2 = 0.0;
-    for (long j = 0; j < total; j += KF_DEPTH) {
-#pragma unroll
-        for (int d = 0; d < KF_DEPTH; d++) {
-            const int4 v0 = r0[d], v1 = r1[d];
-            const int s = sh[d];
-            load_next(r0[d], r1[d], sh[d]);
-            if (j + d < total) {
-                const int w[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-                double dx[8], dy[8];
-#pragma unroll
-                for (int k = 0; k < 8; k++) dx[k] = (double)__builtin_amdgcn_ubfe((unsigned)w[k], (unsigned)s, 8u) - m;
-#pragma unroll
-                for (int k = 0; k < 8; k++) dy[k] = MODE == 1 ? dx[k] : row_next(dx[k]);
-                if (MODE == 2) {  // timing experiment only (re-associated, NOT the reference's result)
-#pragma unroll
-                    for (int k = 0; k < 8; k += 2) {
-                        acc_n = acc_n + dx[k] * dy[k];
-                        acc_d = acc_d + dx[k] * dx[k];
-                        acc_n2 = acc_n2 + dx[k + 1] * dy[k + 1];
-                        acc_d2 = acc_d2 + dx[k + 1] * dx[k + 1];
-                    }
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 8; k++) {
-                        acc_n = acc_n + dx[k] * dy[k];
-                        acc_d = acc_d + dx[k] * dx[k];
-                    }
-                }
-            }
-        }
-    }
-    if (MODE == 2) {
-        acc_n = acc_n + acc_n2;
-        acc_d = acc_d + acc_d2;
-    }
-    if ((lane & 15) < 15 && f < F) {
-        d2[f] = acc_d;
-        if (f + 1 < F) num[f] = acc_n;
-    }
-}
-
-// Producer/consumer form (default).  The chain adds are the only sequential part; everything else per element
+// Producer/consumer form.  The chain adds are the only sequential part; everything else per element
 // (extract, convert, subtract, neighbour move, two multiplies) is independent across elements.  A workgroup of
-// 4 waves serves the same 60 frames: waves 1-3 compute the rounded products (x-m_f)(x'-m_{f+1}) and (x-m_f)^2
+// 4 waves serves the same frames: waves 1-3 compute the rounded products (x-m_f)(x'-m_{f+1}) and (x-m_f)^2
 // of a stage of KF_STAGE elements into LDS, wave 0 only adds them in sequence order (one LDS read + two adds per
-// element), double-buffered with one barrier per stage.  Same terms, same order: bit-identical to the lane form.
+// element), double-buffered with one barrier per stage.  Same terms, same order as one lane running both chains
+// over its frame (the lane form, 60 frames per wave).
 // Measured (1,000 random 1080p frames, one MI355X): lane form 175 ms; this form with 60 frames per workgroup
 // 122 ms (consumer idle: 130 ms, producers idle: 70 ms; 4 producers or a 4-stage fetch ring: no change), with
 // 30 frames 89 ms, with 15 frames 84 ms (default: 15 frames = one DPP row per workgroup, the other rows mirror
 // it) -- the 60 scattered frame streams of one CU were limited by that CU's outstanding misses; 70 ms is the
 // consumer's floor (one LDS read and two chained fp64 adds per element).
-template <int MODE, int KF_PRODUCERS, int KF_ROWS_PER_PRODUCER, int KF_PD, int KF_DPP_ROWS>
+template <int KF_PRODUCERS, int KF_ROWS_PER_PRODUCER, int KF_PD, int KF_DPP_ROWS>
 __global__ __launch_bounds__(512) void pearson_chain_pc_kernel(const int32_t *__restrict__ rgb, int F, int tm_w,
                                                                int tm_h, const unsigned long long *__restrict__ sums,
                                                                double *__restrict__ d2, double *__restrict__ num) {
@@ -228,21 +150,18 @@ __global__ __launch_bounds__(512) void pearson_chain_pc_kernel(const int32_t *__
                         cs[i] = ns[q][i];
                     }
                     if (st + KF_PD < nstage) fetch(n0[q], n1[q], ns[q]);
-                    if (MODE != 5) {  // MODE 5: timing experiment, producers idle (results invalid)
-                        double2 *buf = &s_t[st & 1][0][0];
+                    double2 *buf = &s_t[st & 1][0][0];
 #pragma unroll
-                        for (int i = 0; i < KF_ROWS_PER_PRODUCER; i++) {
-                            const int wv[8] = {c0[i].x, c0[i].y, c0[i].z, c0[i].w, c1[i].x, c1[i].y, c1[i].z, c1[i].w};
+                    for (int i = 0; i < KF_ROWS_PER_PRODUCER; i++) {
+                        const int wv[8] = {c0[i].x, c0[i].y, c0[i].z, c0[i].w, c1[i].x, c1[i].y, c1[i].z, c1[i].w};
 #pragma unroll
-                            for (int e = 0; e < 8; e++) {
-                                // (double)x exactly, without v_cvt_f64_u32: 2^52 + x built from its bits, minus 2^52
-                                const double xb = __hiloint2double(
-                                    0x43300000, (int)__builtin_amdgcn_ubfe((unsigned)wv[e], (unsigned)cs[i], 8u));
-                                const double dx = (xb - 4503599627370496.0) - m;
-                                const double dy = row_next(dx);
-                                buf[((p * KF_ROWS_PER_PRODUCER + i) * 8 + e) * 64 + lane] =
-                                    make_double2(dx * dy, dx * dx);
-                            }
+                        for (int e = 0; e < 8; e++) {
+                            // (double)x exactly, without v_cvt_f64_u32: 2^52 + x built from its bits, minus 2^52
+                            const double xb = __hiloint2double(
+                                0x43300000, (int)__builtin_amdgcn_ubfe((unsigned)wv[e], (unsigned)cs[i], 8u));
+                            const double dx = (xb - 4503599627370496.0) - m;
+                            const double dy = row_next(dx);
+                            buf[((p * KF_ROWS_PER_PRODUCER + i) * 8 + e) * 64 + lane] = make_double2(dx * dy, dx * dx);
                         }
                     }
                     __syncthreads();
@@ -257,8 +176,7 @@ __global__ __launch_bounds__(512) void pearson_chain_pc_kernel(const int32_t *__
         for (long st = 0; st < nstage; st++) {
             const double2 *buf = &s_t[st & 1][0][0];
             const long left = (total - st * KF_STAGE_ROWS) * 8;
-            if (MODE == 4) {  // timing experiment: consumer idle (results invalid)
-            } else if (left >= KF_STAGE) {
+            if (left >= KF_STAGE) {
 #pragma unroll 8
                 for (int e = 0; e < KF_STAGE; e++) {
                     const double2 t = buf[e * 64 + lane];
@@ -312,7 +230,7 @@ int interframe_corr_dev(const int32_t *d_rgb, int F, int tm_w, int tm_h, double 
             KTimer tm("kf_corr", stream);
             {
                 const int per = 15;  // frames per workgroup (one DPP row; see the kernel)
-                hipLaunchKernelGGL((pearson_chain_pc_kernel<0, 3, 3, 2, 1>), dim3((F + per - 1) / per), dim3(256), 0,
+                hipLaunchKernelGGL((pearson_chain_pc_kernel<3, 3, 2, 1>), dim3((F + per - 1) / per), dim3(256), 0,
                                    stream, d_rgb, F, tm_w, tm_h, d_sums, d_d2, d_num);
             }
             if (hipGetLastError() != hipSuccess) break;

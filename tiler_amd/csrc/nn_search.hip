@@ -432,26 +432,21 @@ __global__ __launch_bounds__(256) void prep16_kernel(Prep16Args a) {
 // FLAT: a workgroup whose queries are all flat tiles (grouped last by nn_frame_tiling_dev; their fragments are zero
 // beyond k-step 0, dc_first_dim): per candidate block only k-step 0 is streamed (1 of S KB) and contracted, the
 // same keys bit for bit.
-// MODE (timing experiments of the experiment build only; results invalid when != 0): 1 no list insertion, 2 no
-// epilogue, 3 no epilogue and no A-fragment reads inside the stage (the MFMA + stream floor)
-template <int N>
-__device__ __forceinline__ void vm_wait() {  // s_waitcnt vmcnt(N): all but this wave's N youngest vector-memory ops
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// VAR bit 0: per query block, a wave-uniform test before its 4 per-element list tests, thresholds kept in registers
-// (the same comparisons, so the same lists); bit 1: a 3-buffer LDS ring (two stages in flight instead of one).
+// Per query block, a wave-uniform test comes before its 4 per-element list tests, the thresholds kept in registers (the
+// same comparisons as testing each element against the list's last key, so the same lists; r04c/r04e: -2..-3 %
+// shortlist time, same digests).
 // Measured and removed (round 5, DESIGN.md section 4, identical digests): a software-pipelined stage (block cb + 1's
 // MFMAs before block cb's epilogue, one compare per element) +1.5..3 %; 4 blocks per stage +1..3 %; 4 blocks per
-// stage with the insertions queued per lane in LDS and applied in bulk +6 % (commit c152f52 has both).
-// gate (VAR bit 0 only; nullptr: off): the k = 1 search's exact insertion gate (round 6).  The rescore needs every
+// stage with the insertions queued per lane in LDS and applied in bulk +6 % (commit c152f52 has both); a 3-buffer LDS
+// ring (two stages in flight instead of one), no gain.
+// gate (nullptr: off): the k = 1 search's exact insertion gate (round 6).  The rescore needs every
 // candidate whose key can reach T(kk), kk the smallest key of the query (nn_rescore_kernel; T increasing in kk), and
 // T(kk) <= T(b) for every key b the query has already seen.  So a lane may skip any candidate whose key exceeds
 // T(best key of the query so far, over its 4 lanes): gate[q] = (x, y) with T(b) <= (b + x) * gb + y up to the
 // fp32 slack added here (gate16_kernel).  Each lane's own L-th key still gates its list as before; the tighter of the
 // two is kept current in th[] whenever the wave takes the insertion branch (the 4 lanes' bests by two xor shuffles).
 // A lane's list keeps every candidate the rescore can need, so the overflow rule and tiers 2 / 3 are unchanged.
-template <int S, int L, int CB, int NW, int QB, bool FLAT, int MODE = 0, int VAR = 0>
+template <int S, int L, int CB, int NW, int QB, bool FLAT>
 __device__ __forceinline__ void shortlist16_body(const half8 *__restrict__ cfrag, const float *__restrict__ cseed,
                                                  int nblk, const half8 *__restrict__ qfrag, int nq, int blk_per_split,
                                                  int nsplit, int perm, float *__restrict__ out_key,
@@ -519,13 +514,7 @@ __device__ __forceinline__ void shortlist16_body(const half8 *__restrict__ cfrag
                        smem + buf * BUF_BYTES + FRAG_BYTES);
     };
 
-    constexpr int NBUF = (VAR & 2) ? 3 : 2;
-    // a stage's DMA instructions per wave (the seed piece is wave 0's): the counted wait of the 3-buffer ring
-    auto wait_all_but_next = [&]() {
-        if (w == 0) vm_wait<(FLAT ? 1 : PER_T) + 1>();
-        else vm_wait<(FLAT ? 1 : PER_T)>();
-    };
-    float th[QB];  // VAR & 1: max(-0.5 * lk[q][L - 1], the gate's bound), kept current
+    float th[QB];  // max(-0.5 * lk[q][L - 1], the gate's bound), kept current
     float2 gq[QB];  // the gate of this lane's query of block q (x = +inf: none)
 #pragma unroll
     for (int q = 0; q < QB; q++) {
@@ -534,15 +523,10 @@ __device__ __forceinline__ void shortlist16_body(const half8 *__restrict__ cfrag
         gq[q] = (gate && qq < nq) ? gate[qq] : make_float2(INFINITY, INFINITY);
     }
     if (nstage > 0) issue(0, 0);
-    if (NBUF == 3 && nstage > 1) {
-        issue(1, 1);
-        wait_all_but_next();
-    } else {
-        dma_drain();
-    }
+    dma_drain();
     __syncthreads();
     for (int st = 0; st < nstage; st++) {
-        const char *B = smem + (st % NBUF) * BUF_BYTES;
+        const char *B = smem + (st & 1) * BUF_BYTES;
         const half8 *A = reinterpret_cast<const half8 *>(B) + lane;
         const floatx4 *SD = reinterpret_cast<const floatx4 *>(B + FRAG_BYTES) + g;
         floatx4 sd[CB];
@@ -550,7 +534,7 @@ __device__ __forceinline__ void shortlist16_body(const half8 *__restrict__ cfrag
         for (int cb = 0; cb < CB; cb++) sd[cb] = SD[cb * 4];
         half8 a0 = A[0], a1 = A[64];
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (st + NBUF - 1 < nstage) issue(st + NBUF - 1, (st + NBUF - 1) % NBUF);
+        if (st + 1 < nstage) issue(st + 1, (st + 1) & 1);
 #pragma unroll
         for (int cb = 0; cb < CB; cb++) {
             const int blk = b_begin + st * CB + cb;
@@ -565,9 +549,8 @@ __device__ __forceinline__ void shortlist16_body(const half8 *__restrict__ cfrag
 #pragma unroll
                 for (int s = 0; s < S; s += 2) {
                     half8 n0, n1;
-                    const bool more = MODE != 3 && (s + 2 < S || cb + 1 < CB);
-                    if constexpr (MODE == 3) {
-                    } else if (s + 2 < S) {
+                    const bool more = s + 2 < S || cb + 1 < CB;
+                    if (s + 2 < S) {
                         n0 = A[(cb * S + s + 2) * 64];
                         n1 = A[(cb * S + s + 3) * 64];
                     } else if (cb + 1 < CB) {
@@ -588,64 +571,43 @@ __device__ __forceinline__ void shortlist16_body(const half8 *__restrict__ cfrag
                     }
                 }
                 }
-                if constexpr (MODE >= 2) {
-#pragma unroll
-                    for (int q = 0; q < QB; q++) li[q][0] += __float_as_int(acc[q][0]) & 1;  // keeps the MFMAs live
-                    continue;
-                }
                 // epilogue: acc = q.c - ||c||^2/2, key = -2 acc; one wave-uniform branch per block
                 bool need = false;
                 float m[QB];
 #pragma unroll
                 for (int q = 0; q < QB; q++) {
                     m[q] = fmaxf(fmaxf(acc[q][0], acc[q][1]), fmaxf(acc[q][2], acc[q][3]));
-                    need |= m[q] > ((VAR & 1) ? th[q] : -0.5f * lk[q][L - 1]);
-                }
-                if constexpr (MODE == 1) {
-                    li[0][0] += need ? 1 : 0;
-                    continue;
+                    need |= m[q] > th[q];
                 }
                 if (__builtin_expect(__any(need), 0)) {
                     const int base = blk * 16;
-                    if constexpr ((VAR & 1) != 0) {
 #pragma unroll
-                        for (int q = 0; q < QB; q++)
-                            if (__any(m[q] > th[q]))
-#pragma unroll
-                                for (int i = 0; i < 4; i++)
-                                    if (acc[q][i] > th[q]) {
-                                        list_insert<L>(lk[q], li[q], -2.0f * acc[q][i], base + rel[i]);
-                                        th[q] = fmaxf(th[q], -0.5f * lk[q][L - 1]);
-                                    }
-                        if (gate) {  // wave-uniform: the query's best key over its 4 lanes -> its gate
-#pragma unroll
-                            for (int q = 0; q < QB; q++) {
-                                float b = lk[q][0];
-                                b = fminf(b, __shfl_xor(b, 16, 64));
-                                b = fminf(b, __shfl_xor(b, 32, 64));
-                                if (gq[q].x < INFINITY && b < INFINITY) {
-                                    const float X = b + gq[q].x, T1 = X * gb, T2 = T1 + gq[q].y;
-                                    // every rounding of the three ops, and the rescore's 1e-12 |kk| term, inside
-                                    const float T = T2 + (fabsf(T1) + fabsf(gq[q].y)) * 9.5367431640625e-07f + 1e-30f;
-                                    th[q] = fmaxf(th[q], -0.5f * T);
-                                }
-                            }
-                        }
-                    } else {
-#pragma unroll
-                        for (int q = 0; q < QB; q++)
+                    for (int q = 0; q < QB; q++)
+                        if (__any(m[q] > th[q]))
 #pragma unroll
                             for (int i = 0; i < 4; i++)
-                                if (acc[q][i] > -0.5f * lk[q][L - 1])
+                                if (acc[q][i] > th[q]) {
                                     list_insert<L>(lk[q], li[q], -2.0f * acc[q][i], base + rel[i]);
+                                    th[q] = fmaxf(th[q], -0.5f * lk[q][L - 1]);
+                                }
+                    if (gate) {  // wave-uniform: the query's best key over its 4 lanes -> its gate
+#pragma unroll
+                        for (int q = 0; q < QB; q++) {
+                            float b = lk[q][0];
+                            b = fminf(b, __shfl_xor(b, 16, 64));
+                            b = fminf(b, __shfl_xor(b, 32, 64));
+                            if (gq[q].x < INFINITY && b < INFINITY) {
+                                const float X = b + gq[q].x, T1 = X * gb, T2 = T1 + gq[q].y;
+                                // every rounding of the three ops, and the rescore's 1e-12 |kk| term, inside
+                                const float T = T2 + (fabsf(T1) + fabsf(gq[q].y)) * 9.5367431640625e-07f + 1e-30f;
+                                th[q] = fmaxf(th[q], -0.5f * T);
+                            }
+                        }
                     }
                 }
             }
         }
-        if (NBUF == 3 && st + 2 < nstage)
-            wait_all_but_next();  // stage st + 1 landed, st + 2 may still be in flight
-        else
-            dma_drain();
+        dma_drain();
         __syncthreads();
     }
     // partial lists: [q][split][g][L]
@@ -664,7 +626,7 @@ __device__ __forceinline__ void shortlist16_body(const half8 *__restrict__ cfrag
 }
 
 // flat_cnt (or null): device count of the batch's non-flat queries, the flat ones placed after them
-template <int S, int L, int CB, int NW, int QB, int MODE = 0, int VAR = 0>
+template <int S, int L, int CB, int NW, int QB>
 __global__ __launch_bounds__(NW * 64, 1) void nn_shortlist16_kernel(const half8 *__restrict__ cfrag,
                                                                 const float *__restrict__ cseed, int nblk,
                                                                 const half8 *__restrict__ qfrag, int nq,
@@ -673,11 +635,11 @@ __global__ __launch_bounds__(NW * 64, 1) void nn_shortlist16_kernel(const half8 
                                                                 int *__restrict__ out_idx, const int *flat_cnt,
                                                                 const float2 *__restrict__ gate, float gb) {
     if (flat_cnt && (long)blockIdx.x * (NW * QB * 16) >= (long)*flat_cnt)
-        shortlist16_body<S, L, CB, NW, QB, true, MODE, VAR>(cfrag, cseed, nblk, qfrag, nq, blk_per_split, nsplit, perm,
-                                                            out_key, out_idx, gate, gb);
+        shortlist16_body<S, L, CB, NW, QB, true>(cfrag, cseed, nblk, qfrag, nq, blk_per_split, nsplit, perm, out_key,
+                                                 out_idx, gate, gb);
     else
-        shortlist16_body<S, L, CB, NW, QB, false, MODE, VAR>(cfrag, cseed, nblk, qfrag, nq, blk_per_split, nsplit,
-                                                             perm, out_key, out_idx, gate, gb);
+        shortlist16_body<S, L, CB, NW, QB, false>(cfrag, cseed, nblk, qfrag, nq, blk_per_split, nsplit, perm, out_key,
+                                                  out_idx, gate, gb);
 }
 
 // The k = 1 gate of nn_shortlist16_kernel: T(kk) <= (kk + x) * gb + y for the rescore's threshold
@@ -1762,28 +1724,12 @@ static void launch_shortlist(NNIndex *ix, int nq, int nsplit, int bps, hipStream
                        ix->scratch.key, ix->scratch.idx);
 }
 
-// D=192 generic shortlist variant (A/B switch TILER_SHORTLIST, datasets without mirror orbits; C3 keyframe,
-// one box): "q16" (default): nn_shortlist16_kernel, 16x16x32 MFMA, L16 = 4 (51.6 ms); "q16l6": L16 = 6
-// (53.4 ms, fewer tier-2 queries); "w8": nn_shortlist_kernel, 32x32x16, 8 waves x 2 query blocks (63.9 ms)
-
-
-static int shortlist_variant() {
-    return 16;  // the shipped library: q16 only
-}
-
-// 16x16x32 shortlist for D = 161..192 float datasets: TILER_SHORTLIST=q16 (L16 = 4) / q16l6 (L16 = 6);
-// returns L16, or 0 for the 32x32x16 kernels
-// QB = 4 query blocks per wave; 5 (252 VGPRs) measured the same at 388k candidates (r03h: 80.6-81.2 vs 80.9-81.1 ms)
-static constexpr int SL16_NW = 8, SL16_QB = 4, SL16_CB = 8;
-// shortlist16_body VAR of the shipped kernel: the per-query-block insertion gate (r04c/r04e: -2..-3 % shortlist time,
-// same digests; the 3-buffer ring, VAR 2, measured no gain)
-static constexpr int SL16_VAR = 1;
+// 16x16x32 shortlist (nn_shortlist16_kernel) for D = 161..192 float datasets without mirror orbits: SL16_L list
+// entries per lane; QB = 4 query blocks per wave; 5 (252 VGPRs) measured the same at 388k candidates (r03h: 80.6-81.2
+// vs 80.9-81.1 ms)
+static constexpr int SL16_NW = 8, SL16_QB = 4, SL16_CB = 8, SL16_L = 4;
 static std::atomic<int> g_gate16{1};  // tiler_debug_shortlist_gate: the k = 1 insertion gate (A/B timing hook)
-static int shortlist16_L() {
-    const int v = shortlist_variant();
-    return v == 16 ? 4 : v == 166 ? 6 : 0;
-}
-bool nn_generic_takes_flat(const NNIndex *ix) { return ix->S16 > 0 && shortlist16_L() > 0; }
+bool nn_generic_takes_flat(const NNIndex *ix) { return ix->S16 > 0; }
 
 template <int S, int L>
 static int launch_shortlist16(NNIndex *ix, int nq, int nsplit, int bps, bool gated, const int *flat_cnt,
@@ -1801,14 +1747,11 @@ static int launch_shortlist16(NNIndex *ix, int nq, int nsplit, int bps, bool gat
         hipLaunchKernelGGL(gate16_kernel, dim3((nq + 255) / 256), dim3(256), 0, stream, ix->scratch.qstat, nq, ix->d,
                            ix->maxN, ix->maxH, ix->maxE, ix->scratch.gate);
     }
-    auto go = [&](auto kern, int nbuf) {
-        hipLaunchKernelGGL(kern, grid, dim3(SL16_NW * 64), nbuf * buf, stream, (const half8 *)ix->d_frag16,
-                           ix->d_seed16, ix->nblk16, (const half8 *)ix->scratch.qfrag16, nq, bps, nsplit, ix->perm,
-                           ix->scratch.key, ix->scratch.idx, flat_cnt, gated ? (const float2 *)ix->scratch.gate : nullptr,
-                           gb);
-    };
     KTimer tm("nn_shortlist", stream);
-    go(nn_shortlist16_kernel<S, L, SL16_CB, SL16_NW, SL16_QB, 0, SL16_VAR>, 2);
+    hipLaunchKernelGGL((nn_shortlist16_kernel<S, L, SL16_CB, SL16_NW, SL16_QB>), grid, dim3(SL16_NW * 64), 2 * buf, stream,
+                       (const half8 *)ix->d_frag16, ix->d_seed16, ix->nblk16, (const half8 *)ix->scratch.qfrag16, nq, bps,
+                       nsplit, ix->perm, ix->scratch.key, ix->scratch.idx, flat_cnt,
+                       gated ? (const float2 *)ix->scratch.gate : nullptr, gb);
     TILER_HIP_CHECK(hipGetLastError());
     if (flat_cnt) {  // flat_queries of the stats: derived from the device count when they are read
         ix->last.flat_dev = flat_cnt;
@@ -2085,7 +2028,7 @@ static int search_core(NNIndex *ix, RescoreArgs &ra, const float *d_q, int nq, i
     }
     // 32x32x16 shortlist: 2 lanes x L = 8 per query (>= 2x the 4-way mirror near-ties of one tile per
     // lane, row_perm spreads them 2+2); 16x16x32: 4 lanes x L16 (perm16 spreads them 1 per lane)
-    const int v16 = ix->S16 > 0 ? shortlist16_L() : 0;
+    const int v16 = ix->S16 > 0 ? SL16_L : 0;
     const int L = v16 ? v16 : 8;
     const int lpq = v16 ? 4 : 2;
     const int nblk = v16 ? ix->nblk16 : ix->nblk;
@@ -2155,7 +2098,7 @@ static int search_core(NNIndex *ix, RescoreArgs &ra, const float *d_q, int nq, i
         }
         TILER_HIP_CHECK(hipGetLastError());
         {
-            if (launch_shortlist16<6, 4>(ix, nq, nsplit, bps, k == 1 && g_gate16.load(std::memory_order_relaxed),
+            if (launch_shortlist16<6, SL16_L>(ix, nq, nsplit, bps, k == 1 && g_gate16.load(std::memory_order_relaxed),
                                          opt.flat_cnt, stream))
                 return -1;
         }

@@ -40,28 +40,11 @@ static constexpr int OS = 12;   // k-steps of 16 (4 isotypic blocks x 3)
 #ifndef ORB_STG_ROWS
 #define ORB_STG_ROWS 4  // nn_orbit_rescore_kernel: candidate rows staged in LDS per pass
 #endif
-#ifndef ORB_PR_WAVES
-#define ORB_PR_WAVES 0  // nn_orbit_pairs_kernel: waves per SIMD it is compiled for (0: the compiler's choice)
-#endif
 #ifndef ORB_PR_UNROLL
 #define ORB_PR_UNROLL 8  // nn_orbit_pairs_kernel: 16-byte load pairs in flight per lane
 #endif
 #ifndef ORB_DU
 #define ORB_DU 4
-#endif
-#ifndef ORB_RS_DPP
-#define ORB_RS_DPP 1  // rescore / pair pass reductions: DPP lane moves inside each row of 16, one ds_bpermute across rows
-#endif
-#ifndef ORB_SPLIT_TAILS
-// 1: the shortlist in two query halves, the first half's rescore + pair pass on a second stream beside the second
-// launch.  Measured (r06z, profiles/r06/z_split_tails_ab.txt, same box, same digest): C3 step 14.75 -> 14.61 ms, but the
-// second launch absorbs the overlapped tails (shortlist 13.07 -> 13.40 ms, roofline.frac 0.458 -> 0.44) and the
-// tails' own event times stop meaning their cost; a 1 % step gain does not pay for measurements that no longer
-// isolate the kernels, so it stays off (an A/B switch)
-#define ORB_SPLIT_TAILS 0
-#endif
-#ifndef ORB_PR_QUAD
-#define ORB_PR_QUAD 1  // nn_orbit_pairs_kernel: the query row loaded once per quad of slot lanes, broadcast by DPP (r06o: 0.50 -> 0.42 ms)
 #endif
 
 // device copy of the transform: output coordinate o (block x = o / 48) = coef[o] * sum_t w[o][t] * v[src[o][t]]
@@ -528,200 +511,18 @@ __global__ __launch_bounds__(64 * ORB_PW) void orbit_prep_kernel(OrbitPrepArgs a
 }
 
 // ------------------------------------------------------------------------------------------
-// device: the orbit shortlist.  Workgroup = NW waves x one 32-query block; the 32-tile blocks of this
-// split stream through a double-buffered LDS ring (CB blocks per stage, LDS-DMA).  Accumulator element
-// r of lane l holds tile row (r & 3) + 8 (r >> 2) + 4 h (h = l >> 5) of query column l & 31; sub-block
-// s = r >> 2 = the 4 consecutive tiles 8 s + 4 h + 0..3.  List entry id = blk * 4 + s.
-// ------------------------------------------------------------------------------------------
-template <int L, int CB, int NW, int QB, int MODE>
-__global__ __launch_bounds__(NW * 64, 1) void nn_orbit_shortlist_kernel(const half8 *__restrict__ cfrag,
-                                                                    const float *__restrict__ cseed, int nblk,
-                                                                    const half8 *__restrict__ qfrag, int nq,
-                                                                    int blk_per_split, int nsplit,
-                                                                    float *__restrict__ out_key,
-                                                                    int *__restrict__ out_id) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int FRAG_BYTES = CB * OS * 1024;
-    constexpr int BUF_BYTES = FRAG_BYTES + CB * 128;
-    constexpr int NT = NW * 64;
-    constexpr int PER_T = CB * OS * 64 / NT;
-    static_assert((CB * OS * 64) % NT == 0, "stage must split evenly over the workgroup");
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, h = lane >> 5;
-    const int nqblk = (nq + 31) / 32;
-    const int qb0 = (blockIdx.x * NW + w) * QB;
-    const int split = blockIdx.y;
-    const int b_begin = split * blk_per_split;
-    const int b_end = min(nblk, b_begin + blk_per_split);
-
-    // the wave's QB query blocks stay in registers as B fragments; each A fragment read from LDS feeds QB MFMAs
-    half8 bq[QB][OS];
-#pragma unroll
-    for (int q = 0; q < QB; q++) {
-        const long qa = min(qb0 + q, nqblk - 1);  // past the end: clamped duplicate, never written
-#pragma unroll
-        for (int s = 0; s < OS; s++) bq[q][s] = qfrag[(qa * OS + s) * 64 + lane];
-    }
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) before the hidden DMA starts counting
-    float lk[QB][L];
-    int li[QB][L];
-#pragma unroll
-    for (int q = 0; q < QB; q++)
-#pragma unroll
-        for (int i = 0; i < L; i++) {
-            lk[q][i] = INFINITY;
-            li[q][i] = -1;
-        }
-
-    const int nstage = (b_end > b_begin) ? (b_end - b_begin + CB - 1) / CB : 0;
-    auto issue = [&](int st, int buf) {
-        const int blk0 = b_begin + st * CB;
-        const int nb = min(CB, b_end - blk0);
-        const uint4 *src = reinterpret_cast<const uint4 *>(cfrag) + (long)blk0 * OS * 64 + w * 64 + lane;
-        char *dst = smem + buf * BUF_BYTES + w * 1024;
-        if (nb == CB) {
-#pragma unroll
-            for (int j = 0; j < PER_T; j++) glds16_asm(src + j * NT, dst + j * NT * 16);
-        } else {
-            const int last = nb * OS * 64 - 1 - (w * 64 + lane);
-#pragma unroll
-            for (int j = 0; j < PER_T; j++) glds16_asm(src + min(j * NT, last), dst + j * NT * 16);
-        }
-        if (w == 0 && lane < CB * 8)
-            glds16_asm(reinterpret_cast<const uint4 *>(cseed) + (long)blk0 * 8 + min(lane, nb * 8 - 1),
-                       smem + buf * BUF_BYTES + FRAG_BYTES);
-    };
-
-    if (nstage > 0) issue(0, 0);
-    dma_drain();
-    __syncthreads();
-    const floatx16 zero = {0};
-    for (int st = 0; st < nstage; st++) {
-        const char *B = smem + (st & 1) * BUF_BYTES;
-        const half8 *A = reinterpret_cast<const half8 *>(B) + lane;
-        const float4 *SD = reinterpret_cast<const float4 *>(B + FRAG_BYTES) + h * 4;
-        half8 a0 = A[0], a1 = A[64];
-        float4 sd0 = SD[0], sd1 = SD[1], sd2 = SD[2], sd3 = SD[3];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (st + 1 < nstage) issue(st + 1, (st + 1) & 1);
-#pragma unroll
-        for (int cb = 0; cb < CB; cb++) {
-            const int blk = b_begin + st * CB + cb;
-            if (blk < b_end) {
-                const floatx16 seed = {sd0.x, sd0.y, sd0.z, sd0.w, sd1.x, sd1.y, sd1.z, sd1.w,
-                                       sd2.x, sd2.y, sd2.z, sd2.w, sd3.x, sd3.y, sd3.z, sd3.w};
-                // p = d0 (seeded with -||c||^2/2), then p += |d_x| as each isotypic block x = 1..3 completes;
-                // blocks 1 and 3 accumulate in ta, block 2 in tb (the next block's MFMAs run while p reads the last)
-                floatx16 p[QB], ta[QB], tb[QB];
-#pragma unroll
-                for (int s = 0; s < OS; s += 2) {
-                    half8 n0, n1;
-                    const bool more = s + 2 < OS || cb + 1 < CB;
-                    if (s + 2 < OS) {
-                        n0 = A[(cb * OS + s + 2) * 64];
-                        n1 = A[(cb * OS + s + 3) * 64];
-                    } else if (cb + 1 < CB) {  // next block of this stage: first pair and seeds
-                        n0 = A[((cb + 1) * OS) * 64];
-                        n1 = A[((cb + 1) * OS + 1) * 64];
-                        sd0 = SD[(cb + 1) * 8 + 0];
-                        sd1 = SD[(cb + 1) * 8 + 1];
-                        sd2 = SD[(cb + 1) * 8 + 2];
-                        sd3 = SD[(cb + 1) * 8 + 3];
-                    }
-#pragma unroll
-                    for (int hh = 0; hh < 2; hh++) {
-                        const int ss = s + hh, x = ss / 3;
-                        const half8 av = hh ? a1 : a0;
-#pragma unroll
-                        for (int q = 0; q < QB; q++) {
-                            if (x == 0)
-                                p[q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, bq[q][ss], ss == 0 ? seed : p[q], 0, 0, 0);
-                            else if (x == 2)
-                                tb[q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, bq[q][ss], ss % 3 == 0 ? zero : tb[q], 0, 0, 0);
-                            else
-                                ta[q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, bq[q][ss], ss % 3 == 0 ? zero : ta[q], 0, 0, 0);
-                        }
-                        if (MODE != 3 && x > 0 && ss % 3 == 2) {
-#pragma unroll
-                            for (int q = 0; q < QB; q++)
-#pragma unroll
-                                for (int r = 0; r < 16; r++) p[q][r] = p[q][r] + fabsf(x == 2 ? tb[q][r] : ta[q][r]);
-                        }
-                    }
-                    if (more) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x008, 2 * QB, 0);
-                    if (more) {
-                        a0 = n0;
-                        a1 = n1;
-                    }
-                }
-#pragma unroll
-                for (int q = 0; q < QB; q++) {
-                    if (MODE == 3) {  // timing experiment: MFMA only
-                        lk[q][0] = fmaxf(lk[q][0], p[q][0] + ta[q][1] + tb[q][2]);
-                        continue;
-                    }
-                    // p = u = d0 + |d1| + |d2| + |d3| >= every mirror value q.(S_m c) - ||c||^2/2 (key = -2u)
-                    float m4[4];
-#pragma unroll
-                    for (int sb = 0; sb < 4; sb++)
-                        m4[sb] = fmaxf(fmaxf(p[q][4 * sb], p[q][4 * sb + 1]), fmaxf(p[q][4 * sb + 2], p[q][4 * sb + 3]));
-                    const float mx = fmaxf(fmaxf(m4[0], m4[1]), fmaxf(m4[2], m4[3]));
-                    if (MODE == 2) {  // timing experiment: MFMA + bound only
-                        lk[q][0] = fmaxf(lk[q][0], mx);
-                        continue;
-                    }
-                    if (__builtin_expect(__any(mx > -0.5f * lk[q][L - 1]), 0)) {
-                        // insert every sub-block above the lane's current L-th entry, best first
-#pragma unroll
-                        for (int it = 0; it < 4; it++) {
-                            float best = m4[0];
-                            int bs = 0;
-#pragma unroll
-                            for (int sb = 1; sb < 4; sb++)
-                                if (m4[sb] > best) {
-                                    best = m4[sb];
-                                    bs = sb;
-                                }
-                            const bool ins = best > -0.5f * lk[q][L - 1];
-                            if (!__any(ins)) break;
-                            if (ins) {
-                                list_insert<L>(lk[q], li[q], -2.0f * best, blk * 4 + bs);
-#pragma unroll
-                                for (int sb = 0; sb < 4; sb++)
-                                    if (sb == bs) m4[sb] = -INFINITY;
-                            }
-                        }
-                    }
-                }
-            }
-        }
-        dma_drain();
-        __syncthreads();
-    }
-#pragma unroll
-    for (int q = 0; q < QB; q++) {
-        const int qq = (qb0 + q) * 32 + (lane & 31);
-        if (qb0 + q < nqblk && qq < nq) {
-            const long o = (((long)qq * nsplit + split) * 2 + h) * L;
-#pragma unroll
-            for (int i = 0; i < L; i++) {
-                out_key[o + i] = lk[q][i];
-                out_id[o + i] = li[q][i];
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// device: the orbit shortlist, software-pipelined (default).  Same contraction, bound and lists as
-// nn_orbit_shortlist_kernel, but no block ends in a VALU-only tail: the bound adds of block b run beside
+// device: the orbit shortlist, software-pipelined.  Workgroup = NW waves x QB 32-query blocks each (B
+// fragments in registers); the 32-tile blocks of this split stream through a double-buffered LDS ring (CB
+// blocks per stage, LDS-DMA).  Accumulator element r of lane l holds tile row (r & 3) + 8 (r >> 2) + 4 h
+// (h = l >> 5) of query column l & 31; sub-block s = r >> 2 = the 4 consecutive tiles 8 s + 4 h + 0..3.
+// List entry id = blk * 4 + s.  No block ends in a VALU-only tail: the bound adds of block b run beside
 // its own x2/x3 MFMAs, and its last |d_3| adds, sub-block maxima and list test run beside block b+1's
 // x0/x1 MFMAs.  Accumulator roles alternate between even and odd blocks so that nothing extra is live:
 //     x0 -> P (seeded), x1 -> RB, x2 -> T2, x3 -> RB,   P = RA, T2 = RC on even blocks, swapped on odd,
 // i.e. the previous block's P is this block's T2 (written only after the previous tail has read it).
 // A list insertion for block b happens right after block b+1's front half (the branch is wave-uniform).
 // ------------------------------------------------------------------------------------------
-template <int L, int CB, int NW, int QB, int MODE>
+template <int L, int CB, int NW, int QB>
 __global__ __launch_bounds__(NW * 64, 1) void nn_orbit_shortlist_pipe_kernel(const half8 *__restrict__ cfrag,
                                                                          const float *__restrict__ cseed, int nblk,
                                                                          const half8 *__restrict__ qfrag, int nq,
@@ -754,12 +555,6 @@ __global__ __launch_bounds__(NW * 64, 1) void nn_orbit_shortlist_pipe_kernel(con
         for (int s = 0; s < OS; s++) bq[q][s] = qfrag[(qa * OS + s) * 64 + lane];
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) before the hidden DMA starts counting
-    if (NW * QB > 8 * 2 / 2 && NW == 4) {  // experiment (one wave per SIMD): the B fragments live in the AGPR file
-#pragma unroll
-        for (int q = 0; q < QB; q++)
-#pragma unroll
-            for (int s = 0; s < OS; s++) asm volatile("" : "+a"(bq[q][s]));
-    }
     float lk[QB][L], th[QB];
     int li[QB][L];
 #pragma unroll
@@ -918,31 +713,18 @@ __global__ __launch_bounds__(NW * 64, 1) void nn_orbit_shortlist_pipe_kernel(con
     if (nstage > 0) issue(0, 0);
     dma_drain();
     __syncthreads();
-    if ((MODE == 3 || MODE == 5 || MODE == 7) && w >= NW / 2) __builtin_amdgcn_s_setprio(1);  // experiment: static priority, 2nd half
-    // experiment LOOSE (modes 6, 7; no longer launched: its loose keys fill the lists and send queries to the slow
-    // tiers, profiles/r02s_shortlist_ab.txt): a sub-block's bound is the sum of its four per-block maxima,
-    // max_t d0 + max_t |d1| + max_t |d2| + max_t |d3| >= max_t u_t (still rigorous, looser), kept in SA / SC
-    constexpr bool LOOSE = MODE == 6 || MODE == 7;
     const floatx16 zero = {0};
     floatx16 RA[QB], RB[QB], RC[QB];
-    float SA[QB][4], SC[QB][4];
-    float dm[16];  // MODE 11 only
 #pragma unroll
-    for (int i = 0; i < 16; i++) dm[i] = (float)(lane + i);
-#pragma unroll
-    for (int q = 0; q < QB; q++) {
-        RA[q] = RB[q] = RC[q] = zero;
-#pragma unroll
-        for (int sb = 0; sb < 4; sb++) SA[q][sb] = SC[q][sb] = -INFINITY;
-    }
+    for (int q = 0; q < QB; q++) RA[q] = RB[q] = RC[q] = zero;
     int pend = -1;          // the block whose tail is pending (-1: none / not a real block)
     half8 a0, a1;           // A fragments of the next k-step pair
     float4 sd0, sd1, sd2, sd3;  // seeds of the next block
 
     // one block: roles P (x0, seeded), T2 (x2); RB takes x1 and x3.  On entry T2 holds the previous
     // block's bound (minus its |d_3|, which is in RB).
-    auto body = [&](const half8 *A, const float4 *SD, int cb, int blk, floatx16 (&P)[QB], floatx16 (&T2)[QB],
-                    float (&Sc)[QB][4], float (&Sp)[QB][4]) __attribute__((always_inline)) {
+    auto body = [&](const half8 *A, const float4 *SD, int cb, int blk, floatx16 (&P)[QB], floatx16 (&T2)[QB])
+                    __attribute__((always_inline)) {
         const floatx16 seed = {sd0.x, sd0.y, sd0.z, sd0.w, sd1.x, sd1.y, sd1.z, sd1.w,
                                sd2.x, sd2.y, sd2.z, sd2.w, sd3.x, sd3.y, sd3.z, sd3.w};
         float pmx[QB];
@@ -950,16 +732,7 @@ __global__ __launch_bounds__(NW * 64, 1) void nn_orbit_shortlist_pipe_kernel(con
         for (int s = 0; s < OS; s += 2) {
             half8 n0, n1;
             const bool more = s + 2 < OS || cb + 1 < CB;
-            if (MODE == 14 || MODE == 15) {  // timing: no A-fragment LDS reads (the stage's first pair reused; invalid)
-                n0 = a0;
-                n1 = a1;
-                if (s + 2 >= OS && cb + 1 < CB) {
-                    sd0 = SD[(cb + 1) * 8 + 0];
-                    sd1 = SD[(cb + 1) * 8 + 1];
-                    sd2 = SD[(cb + 1) * 8 + 2];
-                    sd3 = SD[(cb + 1) * 8 + 3];
-                }
-            } else if (s + 2 < OS) {
+            if (s + 2 < OS) {
                 n0 = A[(cb * OS + s + 2) * 64];
                 n1 = A[(cb * OS + s + 3) * 64];
             } else if (cb + 1 < CB) {  // next block of this stage: first pair and seeds
@@ -991,52 +764,9 @@ __global__ __launch_bounds__(NW * 64, 1) void nn_orbit_shortlist_pipe_kernel(con
                         if (t >= lo && t < hi) D[t / 16][t % 16] = D[t / 16][t % 16] + fabsf(S[t / 16][t % 16]);
                 };
                 constexpr int N3 = 16 * QB, C1 = (N3 + 2) / 3, C2 = (2 * N3 + 2) / 3;
-                // LOOSE: sub-block maxima of one accumulator (|.| when AB), sub-blocks [lo, hi) of the QB * 4
-                auto mx4 = [&](const floatx16 (&S)[QB], int t, bool ab) __attribute__((always_inline)) {
-                    const int q = t / 4, sb = t % 4;
-                    const float a = ab ? fabsf(S[q][4 * sb]) : S[q][4 * sb], b = ab ? fabsf(S[q][4 * sb + 1]) : S[q][4 * sb + 1];
-                    const float c = ab ? fabsf(S[q][4 * sb + 2]) : S[q][4 * sb + 2], d = ab ? fabsf(S[q][4 * sb + 3]) : S[q][4 * sb + 3];
-                    return fmaxf(fmaxf(a, b), fmaxf(c, d));
-                };
-                constexpr int M3 = 4 * QB, D1 = (M3 + 2) / 3, D2 = (2 * M3 + 2) / 3;
-                if (LOOSE) {
-                    if (ss <= 2) {  // previous block: + max |d_3| (RB) -- before step 3's MFMA writes RB
-#pragma unroll
-                        for (int t = 0; t < M3; t++)
-                            if (t >= (ss == 0 ? 0 : ss == 1 ? D1 : D2) && t < (ss == 0 ? D1 : ss == 1 ? D2 : M3))
-                                Sp[t / 4][t % 4] = Sp[t / 4][t % 4] + mx4(RB, t, true);
-                    }
-                    if (ss >= 3 && ss - 3 < QB) {
-                        const int q = ss - 3;
-                        pmx[q] = fmaxf(fmaxf(Sp[q][0], Sp[q][1]), fmaxf(Sp[q][2], Sp[q][3]));
-                        asm volatile("" ::"v"(pmx[q]));
-                    }
-                    if (ss >= 6 && ss <= 8) {  // this block: max d0 (P) + max |d_1| (RB)
-#pragma unroll
-                        for (int t = 0; t < M3; t++)
-                            if (t >= (ss == 6 ? 0 : ss == 7 ? D1 : D2) && t < (ss == 6 ? D1 : ss == 7 ? D2 : M3))
-                                Sc[t / 4][t % 4] = mx4(P, t, false) + mx4(RB, t, true);
-                    }
-                    if (ss >= 10) {  // this block: + max |d_2| (T2)
-#pragma unroll
-                        for (int t = 0; t < M3; t++)
-                            if (t >= (ss == 10 ? 0 : M3 / 2) && t < (ss == 10 ? M3 / 2 : M3))
-                                Sc[t / 4][t % 4] = Sc[t / 4][t % 4] + mx4(T2, t, true);
-                    }
-                } else if (MODE == 11 || MODE == 12 || MODE == 14) {  // timing experiment: every MFMA chain live + (11) as many VALU adds on registers no MFMA touches (12: none)
-                    const int nd = (MODE == 12 || MODE == 14) ? 0 : ss <= 2 ? 11 : ss <= 4 ? 10 : (ss >= 6 && ss <= 8) ? 11 : ss >= 10 ? 16 : 0;
-#pragma unroll
-                    for (int i = 0; i < nd; i++) asm volatile("v_add_f32 %0, %0, |%1|" : "+v"(dm[i & 15]) : "v"(dm[(i + 5) & 15]));
-#pragma unroll
-                    for (int q = 0; q < QB; q++) {  // keep every MFMA chain live (one use of each finished chain)
-                        if (ss == 2) asm volatile("" ::"v"(P[q][0]));
-                        if (ss == 5 || ss == 11) asm volatile("" ::"v"(RB[q][0]));
-                        if (ss == 8) asm volatile("" ::"v"(T2[q][0]));
-                    }
-                } else if (MODE == 2) {  // timing experiment: MFMA + loads only (results invalid)
-                } else if (ss <= 2)  // previous block: + |d_3| (RB) -- before step 3's MFMA writes RB
+                if (ss <= 2)  // previous block: + |d_3| (RB) -- before step 3's MFMA writes RB
                     acc_abs(T2, RB, ss == 0 ? 0 : ss == 1 ? C1 : C2, ss == 0 ? C1 : ss == 1 ? C2 : N3);
-                if (!LOOSE && MODE != 2 && (MODE < 11 || MODE == 13 || MODE == 15) && (ss == 3 || ss == 4)) {  // previous block: its max for the list test
+                if (ss == 3 || ss == 4) {  // previous block: its max for the list test
 #pragma unroll
                     for (int q = 0; q < QB; q++) {  // query blocks [0, (QB+1)/2) at step 3, the rest at step 4
                         if ((ss == 3) != (q < (QB + 1) / 2)) continue;
@@ -1047,19 +777,10 @@ __global__ __launch_bounds__(NW * 64, 1) void nn_orbit_shortlist_pipe_kernel(con
                         asm volatile("" ::"v"(pmx[q]));
                     }
                 }
-                if (!LOOSE && MODE != 2 && (MODE < 11 || MODE == 13 || MODE == 15) && ss >= 6 && ss <= 8)  // this block: + |d_1| (RB, complete after step 5) -- before step 9
+                if (ss >= 6 && ss <= 8)  // this block: + |d_1| (RB, complete after step 5) -- before step 9
                     acc_abs(P, RB, ss == 6 ? 0 : ss == 7 ? C1 : C2, ss == 6 ? C1 : ss == 7 ? C2 : N3);
-                if (!LOOSE && MODE != 2 && (MODE < 11 || MODE == 15) && ss >= 10)  // this block: + |d_2| (T2, complete after step 8)
+                if (ss >= 10)  // this block: + |d_2| (T2, complete after step 8)
                     acc_abs(P, T2, ss == 10 ? 0 : N3 / 2, ss == 10 ? N3 / 2 : N3);
-                if (MODE == 13 && ss >= 9)  // experiment: the |d_2| adds in thirds over steps 9..11 (after step 9's MFMAs)
-                    acc_abs(P, T2, ss == 9 ? 0 : ss == 10 ? C1 : C2, ss == 9 ? C1 : ss == 10 ? C2 : N3);
-                if (MODE == 4 || MODE == 5) {  // experiment: one MFMA, then up to 6 VALU, twice per step
-#pragma unroll
-                    for (int g = 0; g < QB; g++) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);
-                    }
-                }
                 // program order is the schedule: nothing moves across a step (keeps each accumulator's
                 // live range as written, so the role swap needs no extra registers)
                 __builtin_amdgcn_sched_barrier(0);
@@ -1068,18 +789,13 @@ __global__ __launch_bounds__(NW * 64, 1) void nn_orbit_shortlist_pipe_kernel(con
                 a0 = n0;
                 a1 = n1;
             }
-            if (s == 4 && MODE != 1 && MODE != 2 && (MODE < 11 || MODE == 13)) {
+            if (s == 4) {
                 // the previous block's list update (wave-uniform branch), then the back half
 #pragma unroll
                 for (int q = 0; q < QB; q++)
                     if (__builtin_expect(pend >= 0 && __any(pmx[q] > th[q]), 0)) {
                         float m4[4];
-                        if (LOOSE) {
-#pragma unroll
-                            for (int sb = 0; sb < 4; sb++) m4[sb] = Sp[q][sb];
-                        } else {
-                            maxima(T2[q], m4);  // T2 still holds the previous block's bound until step 6
-                        }
+                        maxima(T2[q], m4);  // T2 still holds the previous block's bound until step 6
                         insert_block(q, m4, pend);
                     }
             }
@@ -1101,8 +817,8 @@ __global__ __launch_bounds__(NW * 64, 1) void nn_orbit_shortlist_pipe_kernel(con
         if (st + 1 < nstage) issue(st + 1, (st + 1) & 1);
 #pragma unroll
         for (int cb = 0; cb < CB; cb += 2) {
-            body(A, SD, cb, p_begin + st * CB + cb, RA, RC, SA, SC);
-            body(A, SD, cb + 1, p_begin + st * CB + cb + 1, RC, RA, SC, SA);
+            body(A, SD, cb, p_begin + st * CB + cb, RA, RC);
+            body(A, SD, cb + 1, p_begin + st * CB + cb + 1, RC, RA);
         }
         dma_drain();
         __syncthreads();
@@ -1111,18 +827,10 @@ __global__ __launch_bounds__(NW * 64, 1) void nn_orbit_shortlist_pipe_kernel(con
     if (pend >= 0) {
 #pragma unroll
         for (int q = 0; q < QB; q++) {
-            float m4[4], mx;
-            if (LOOSE) {
+            float m4[4];
 #pragma unroll
-                for (int sb = 0; sb < 4; sb++)
-                    m4[sb] = SC[q][sb] + fmaxf(fmaxf(fabsf(RB[q][4 * sb]), fabsf(RB[q][4 * sb + 1])),
-                                               fmaxf(fabsf(RB[q][4 * sb + 2]), fabsf(RB[q][4 * sb + 3])));
-                mx = fmaxf(fmaxf(m4[0], m4[1]), fmaxf(m4[2], m4[3]));
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; r++) RC[q][r] = RC[q][r] + fabsf(RB[q][r]);
-                mx = maxima(RC[q], m4);
-            }
+            for (int r = 0; r < 16; r++) RC[q][r] = RC[q][r] + fabsf(RB[q][r]);
+            const float mx = maxima(RC[q], m4);
             if (__any(mx > th[q])) insert_block(q, m4, pend);
         }
     }
@@ -1138,9 +846,6 @@ __global__ __launch_bounds__(NW * 64, 1) void nn_orbit_shortlist_pipe_kernel(con
             }
         }
     }
-    if (MODE == 11 || MODE == 12 || MODE == 14)  // timing modes: the dummy adds stay live; the lists stay empty (as MODE 2)
-#pragma unroll
-        for (int i = 0; i < 16; i++) asm volatile("" ::"v"(dm[i]));
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1313,7 +1018,7 @@ __device__ __forceinline__ void orbit_argmin(const OrbitRescoreArgs &a, const fl
     for (int off = WIDTH / 2; off > 0; off >>= 1) {
         float ov;
         int oi, og;
-        if (WIDTH == 4 && ORB_RS_DPP) {  // the pair pass: one lane quad per query, every lane active
+        if (WIDTH == 4) {  // the pair pass: one lane quad per query, every lane active
             ov = __int_as_float(off == 2 ? dpp_mov<0x4E>(__float_as_int(v)) : dpp_mov<0xB1>(__float_as_int(v)));
             oi = off == 2 ? dpp_mov<0x4E>(i) : dpp_mov<0xB1>(i);
             og = off == 2 ? dpp_mov<0x4E>(gs) : dpp_mov<0xB1>(gs);
@@ -1341,19 +1046,15 @@ static constexpr int ORB_PSLOTS = 4; // candidates per query handed to the pair 
 // associative, so any pairing that doubles the reduced span each step works: lane ^ 1 and lane ^ 2 (quad_perm), lane
 // <-> 7 - lane and lane <-> 15 - lane (row half-mirror, row mirror) by DPP -- VALU lane moves, no LDS round trip --
 // then lane ^ 16 by ds_bpermute.  Every lane of the half is active at each call site (the branches around them are
-// uniform over the half-wave).  ORB_RS_DPP 0: five ds_bpermute steps (xor 16, 8, 4, 2, 1) as before (r06r,
-// `profiles/r06/r_rescore_dpp_ab.txt`: rescore 0.540 -> 0.533 ms).
+// uniform over the half-wave).  Five ds_bpermute steps (xor 16, 8, 4, 2, 1) before that (r06r,
+// `profiles/r06/r_rescore_dpp_ab.txt`): rescore 0.540 -> 0.533 ms.
 template <int STEP>  // STEP 0..4: the partner lane of the step
 __device__ __forceinline__ int half_partner(int v) {
-#if ORB_RS_DPP
     if (STEP == 0) return dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]: lane ^ 1
     if (STEP == 1) return dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]: lane ^ 2
     if (STEP == 2) return dpp_mov<0x141>(v);  // row_half_mirror: 7 - lane within 8
     if (STEP == 3) return dpp_mov<0x140>(v);  // row_mirror: 15 - lane within 16
     return __shfl_xor(v, 16, 64);
-#else
-    return __shfl_xor(v, 16 >> STEP, 64);
-#endif
 }
 __device__ __forceinline__ float half_min_f(float v) {
     v = fminf(v, __int_as_float(half_partner<0>(__float_as_int(v))));
@@ -1574,11 +1275,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ORB_RS_WAVE
 // coalesced 32-float column chunks (12 barriers, every slot's row loaded) took 1.00 ms vs 0.50 ms for this per-lane walk.
 // r06o (`profiles/r06/o_pairs_ab.txt`): the query row's 16-byte pieces requested once per quad and broadcast by DPP
 // (exact_dist192_quad) 0.50 -> 0.42 ms at C3, output digest unchanged; the load requests, not HBM, bound this pass.
-#if ORB_PR_WAVES
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ORB_PR_WAVES))) void nn_orbit_pairs_kernel(OrbitRescoreArgs a) {
-#else
 __global__ __launch_bounds__(256) void nn_orbit_pairs_kernel(OrbitRescoreArgs a) {
-#endif
     const long gid = (long)blockIdx.x * 256 + threadIdx.x;
     const long q = gid / ORB_PSLOTS + a.q0;
     const int s = (int)(gid % ORB_PSLOTS);
@@ -1587,19 +1284,14 @@ __global__ __launch_bounds__(256) void nn_orbit_pairs_kernel(OrbitRescoreArgs a)
     const int n = a.pair_cnt[q];
     if (n == 0) return;  // uniform over the group
     int bi = 0x7fffffff, bg = -1;
-#if ORB_PR_QUAD
     static_assert(ORB_PSLOTS == 4, "one lane quad per query");
     {  // every lane of the quad takes part in the broadcasts; a lane past the count re-reads slot 0's row
         const int c = a.pair_cand[q * ORB_PSLOTS + (s < n ? s : 0)];
         const float d = exact_dist192_quad(a.q + q * OD, a.rows + (long)c * OD, s);
         if (s < n) bd = d;
     }
-#endif
     if (s < n) {
         int c = a.pair_cand[q * ORB_PSLOTS + s];
-#if !ORB_PR_QUAD
-        bd = exact_dist192_lean(a.q + q * OD, a.rows + (long)c * OD);
-#endif
         if (a.grp_of) {
             bg = a.grp_of[c];
             class_first(a, a.q + q * OD, c, bg);  // same row, same distance
@@ -1809,8 +1501,7 @@ int orbit_tier2(NNIndex *ix, const float *d_q, const OrbitTail &tail, int nq, hi
 #endif
     // candidate splits: about ORB_T2_WG workgroups in all (128..512 splits); r04t at C3: a fixed 512 splits (one per
     // 4 blocks) gave ~5,600 tiny workgroups, 0.152 ms -> 0.119 ms with ~1,000 (C2 0.059 -> 0.047), digests unchanged
-    const int t2s = ORB_T2_WG > 0 ? std::max(128, std::min(512, ORB_T2_WG / std::max(1, std::min(t2x, (nq + 127) / 128))))
-                                  : 512;
+    const int t2s = std::max(128, std::min(512, ORB_T2_WG / std::max(1, std::min(t2x, (nq + 127) / 128))));
     const int nsplit = std::min(o->gblk, t2s);
     const int bps = (o->gblk + nsplit - 1) / nsplit;
     OrbitCollectArgs ca;
@@ -1862,7 +1553,6 @@ struct FtQueryArgs {
     OrbitStat *qstat;    // [n]
     const float *box;    // [2][192] or null
     float *rootbox;      // [n] when box
-    int xmode;           // 0 (timing-experiment modes of round 2 lived here; results invalid when != 0)
     const int *perm;     // query i reads tile perm[i] (null: tile i)
 };
 
@@ -2122,7 +1812,6 @@ int orbit_ft_queries(NNIndex *ix, const int32_t *d_rgb, int Q, int gamma, float 
     fa.qstat = o->qstat;
     fa.box = box;
     fa.rootbox = rootbox;
-    fa.xmode = 0;
     fa.perm = perm;
     const dim3 grid((unsigned)((Q + 63) / 64));
     KTimer tm("psyv", stream);
@@ -2182,9 +1871,6 @@ void orbit_destroy(OrbitIndex *o, bool synced) {
     dfree(o->d_stats);
     dfree(o->key);
     dfree(o->id);
-    if (o->tail_stream) stream_put(o->tail_stream);
-    if (o->ev_half) (void)hipEventDestroy(o->ev_half);
-    if (o->ev_tail) (void)hipEventDestroy(o->ev_tail);
     delete o;
 }
 
@@ -2448,18 +2134,6 @@ int orbit_search(NNIndex *ix, const float *d_q, int nq, const OrbitTail &tail, h
     if (flat_cnt) mix_full = 0;
     const int bps = (o->gblk + nsplit - 1) / nsplit;
     nsplit = (o->gblk + bps - 1) / bps;
-    // Two query halves (whole rounds of n_cu workgroups first): the first half's rescore and pair pass -- latency-bound
-    // kernels -- run on the index's second stream while the second half's shortlist runs, instead of after it.
-    int split_q = 0;
-    if (ORB_SPLIT_TAILS && !mix_full && wgs >= 2 * n_cu) {
-        const int wa = std::max(1, (wgs / 2 + n_cu / 2) / n_cu) * n_cu;
-        if (wa < wgs && (long)wa * qpw_q < nq) {
-            if (!o->tail_stream) TILER_HIP_CHECK(stream_get(&o->tail_stream));
-            if (!o->ev_half) TILER_HIP_CHECK(hipEventCreateWithFlags(&o->ev_half, hipEventDisableTiming));
-            if (!o->ev_tail) TILER_HIP_CHECK(hipEventCreateWithFlags(&o->ev_tail, hipEventDisableTiming));
-            split_q = wa * qpw_q;
-        }
-    }
     if (orbit_ensure_queries(o, nq)) return -1;
     const size_t nkeys = (size_t)nq * nsplit * 2 * ORB_L;
     if (nkeys > o->cap_keys) {
@@ -2477,52 +2151,26 @@ int orbit_search(NNIndex *ix, const float *d_q, int nq, const OrbitTail &tail, h
     }
     {
         const size_t lds = 2 * ((size_t)ORB_CB * OS * 1024 + ORB_CB * 128);
-        // one timer per launch (the query-half split makes two per search: their per-dispatch times match a trace's)
-        KTimer tm(split_q > 0 ? nullptr : "nn_orbit", stream);
-#define ORB_PIPE(MD)                                                                                              \
-    hipLaunchKernelGGL((nn_orbit_shortlist_pipe_kernel<ORB_L, ORB_CB, ORB_NW, ORB_QB, MD>), dim3(wgs, nsplit),              \
-                       dim3(ORB_NW * 64), lds, stream, (const half8 *)o->d_frag, o->d_seed, o->gblk,                   \
-                       (const half8 *)o->qfrag, nq, bps, nsplit, o->key, o->id, o->red_end, o->d_bmask,                \
-                       0x7fffffff, o->d_bmask0, MD == 0 ? flat_cnt : nullptr, 0)
-        if (!mix_full && split_q == 0) ORB_PIPE(0);
-        if (split_q > 0) {  // two launches over query halves; the end of the first one is the tails' start
-            const int qb_off = split_q / 32;
-            const size_t per_q = (size_t)nsplit * 2 * ORB_L;
-            {
-                KTimer ta("nn_orbit", stream);
-                hipLaunchKernelGGL((nn_orbit_shortlist_pipe_kernel<ORB_L, ORB_CB, ORB_NW, ORB_QB, 0>),
-                                   dim3(split_q / qpw_q, nsplit), dim3(ORB_NW * 64), lds, stream,
-                                   (const half8 *)o->d_frag, o->d_seed, o->gblk, (const half8 *)o->qfrag, split_q, bps,
-                                   nsplit, o->key, o->id, o->red_end, o->d_bmask, 0x7fffffff, o->d_bmask0, flat_cnt, 0);
-            }
-            TILER_HIP_CHECK(hipEventRecord(o->ev_half, stream));
-            KTimer tb("nn_orbit", stream);
-            hipLaunchKernelGGL((nn_orbit_shortlist_pipe_kernel<ORB_L, ORB_CB, ORB_NW, ORB_QB, 0>),
-                               dim3(wgs - split_q / qpw_q, nsplit), dim3(ORB_NW * 64), lds, stream,
-                               (const half8 *)o->d_frag, o->d_seed, o->gblk,
-                               (const half8 *)o->qfrag + (size_t)qb_off * OS * 64, nq - split_q, bps, nsplit,
-                               o->key + (size_t)split_q * per_q, o->id + (size_t)split_q * per_q, o->red_end,
-                               o->d_bmask, 0x7fffffff, o->d_bmask0, flat_cnt, split_q);
-        }
-        if (mix_full) {
-            const int qb_off = mix_full * ORB_NW * ORB_QB, q_off = qb_off * 32;  // query blocks / queries of part A
-            const size_t per_q = (size_t)nsplit * 2 * ORB_L;
+        const size_t per_q = (size_t)nsplit * 2 * ORB_L;  // list entries per query: every launch keeps this stride
+        KTimer tm("nn_orbit", stream);
+        // wg workgroups x ns splits of blk candidate blocks each, over the n queries from query block qb on
+        auto shortlist = [&](int wg, int ns, int qb, int n, int blk, const int *fc) {
+            hipLaunchKernelGGL((nn_orbit_shortlist_pipe_kernel<ORB_L, ORB_CB, ORB_NW, ORB_QB>), dim3(wg, ns),
+                               dim3(ORB_NW * 64), lds, stream, (const half8 *)o->d_frag, o->d_seed, o->gblk,
+                               (const half8 *)o->qfrag + (size_t)qb * OS * 64, n, blk, nsplit,
+                               o->key + (size_t)qb * 32 * per_q, o->id + (size_t)qb * 32 * per_q, o->red_end,
+                               o->d_bmask, 0x7fffffff, o->d_bmask0, fc, 0);
+        };
+        if (!mix_full) {
+            shortlist(wgs, nsplit, 0, nq, bps, flat_cnt);
+        } else {
+            const int qb_off = mix_full * qpw, q_off = qb_off * 32;  // query blocks / queries of part A
             const size_t na = (size_t)std::min(nq, q_off) * per_q;
             TILER_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)o->key, 0x7f800000u, na, stream));  // +inf: empty
             TILER_HIP_CHECK(hipMemsetAsync(o->id, 0xff, na * sizeof(int), stream));
-            hipLaunchKernelGGL((nn_orbit_shortlist_pipe_kernel<ORB_L, ORB_CB, ORB_NW, ORB_QB, 0>), dim3(mix_full, 1),
-                               dim3(ORB_NW * 64), lds, stream, (const half8 *)o->d_frag, o->d_seed, o->gblk,
-                               (const half8 *)o->qfrag, nq, o->gblk, nsplit, o->key, o->id, o->red_end, o->d_bmask,
-                               0x7fffffff, o->d_bmask0, nullptr, 0);
-            if (nq > q_off)
-                hipLaunchKernelGGL((nn_orbit_shortlist_pipe_kernel<ORB_L, ORB_CB, ORB_NW, ORB_QB, 0>),
-                                   dim3(wgs - mix_full, nsplit), dim3(ORB_NW * 64), lds, stream,
-                                   (const half8 *)o->d_frag, o->d_seed, o->gblk,
-                                   (const half8 *)o->qfrag + (size_t)qb_off * OS * 64, nq - q_off, bps, nsplit,
-                                   o->key + (size_t)q_off * per_q, o->id + (size_t)q_off * per_q, o->red_end,
-                                   o->d_bmask, 0x7fffffff, o->d_bmask0, nullptr, 0);
+            shortlist(mix_full, 1, 0, nq, o->gblk, nullptr);
+            if (nq > q_off) shortlist(wgs - mix_full, nsplit, qb_off, nq - q_off, bps, nullptr);
         }
-#undef ORB_PIPE
     }
     TILER_HIP_CHECK(hipGetLastError());
     OrbitRescoreArgs ra;
@@ -2562,34 +2210,18 @@ int orbit_search(NNIndex *ix, const float *d_q, int nq, const OrbitTail &tail, h
         TILER_HIP_CHECK(hipMemsetAsync(o->d_stats, 0, 2 * sizeof(int), stream));
         ra.t.n_expand = o->d_stats;
     }
-    // the rescore and pair pass of queries [q0, q1) on stream s
-    auto tails = [&](int q0, int q1, hipStream_t s) -> int {
-        OrbitRescoreArgs r = ra;
-        r.q0 = q0;
-        r.nq = q1;
-        {
-            KTimer tm("nn_rescore", s);
-            hipLaunchKernelGGL(nn_orbit_rescore_kernel, dim3((unsigned)((q1 - q0 + 7) / 8)), dim3(256), 0, s, r);
-        }
-        TILER_HIP_CHECK(hipGetLastError());
-        {
-            static_assert(256 % ORB_PSLOTS == 0, "pair groups must not straddle blocks");
-            KTimer tm("nn_pairs", s);
-            const long lanes = (long)(q1 - q0) * ORB_PSLOTS;
-            hipLaunchKernelGGL(nn_orbit_pairs_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, r);
-        }
-        TILER_HIP_CHECK(hipGetLastError());
-        return 0;
-    };
-    if (split_q > 0) {
-        TILER_HIP_CHECK(hipStreamWaitEvent(o->tail_stream, o->ev_half, 0));
-        if (tails(0, split_q, o->tail_stream)) return -1;
-        TILER_HIP_CHECK(hipEventRecord(o->ev_tail, o->tail_stream));
-        if (tails(split_q, nq, stream)) return -1;
-        TILER_HIP_CHECK(hipStreamWaitEvent(stream, o->ev_tail, 0));  // tier 2 / 3 and the caller after both halves
-    } else if (tails(0, nq, stream)) {
-        return -1;
+    {
+        KTimer tm("nn_rescore", stream);
+        hipLaunchKernelGGL(nn_orbit_rescore_kernel, dim3((unsigned)((nq + 7) / 8)), dim3(256), 0, stream, ra);
     }
+    TILER_HIP_CHECK(hipGetLastError());
+    {
+        static_assert(256 % ORB_PSLOTS == 0, "pair groups must not straddle blocks");
+        KTimer tm("nn_pairs", stream);
+        const long lanes = (long)nq * ORB_PSLOTS;
+        hipLaunchKernelGGL(nn_orbit_pairs_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, ra);
+    }
+    TILER_HIP_CHECK(hipGetLastError());
     if (want_stats) {
         int h[2];
         TILER_HIP_CHECK(hipMemcpyAsync(h, o->d_stats, sizeof(h), hipMemcpyDeviceToHost, stream));

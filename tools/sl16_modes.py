@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
-"""Timing modes of the generic 16x16x32 shortlist (nn_shortlist16_kernel) on a real PrepareFrameTiling candidate set.
+"""Timing of the generic 16x16x32 shortlist (nn_shortlist16_kernel) on a real PrepareFrameTiling candidate set.
 
 One keyframe of bench_encoder's clip (1080p, 24 frames, items from --item-tiles tiles of a 64k set, Medium quality):
 tiler_prepare_frame_tiling_dev builds its candidate set, then FrameTiling of the keyframe is timed --reps times with
-the kernel timers on; prints the shortlist's HIP-event time and the output digest.  With the experiment library and
-TILER_SL16_MODE=1..3 the shortlist runs a timing mode (results invalid; the search stops after the shortlist, so
-nothing downstream reads them).  Study script (generic shortlist); not part of the product.
+the kernel timers on; prints the shortlist's HIP-event time and the output digest.  --gate 0 / 1 switches the k = 1
+insertion gate, --lib loads another build (A/B).  Study script (generic shortlist); not part of
+the product.
 """
 import argparse
 import ctypes
@@ -85,8 +85,7 @@ def main():
     m0 = info["candidates"]
     flops = 2.0 * (-(-m0 // 16) * 16) * 32 * (6 * (n - st["flat_queries"]) + st["flat_queries"])
     best = min(ms)
-    print(json.dumps({"tag": args.tag, "gate": args.gate, "mode": os.environ.get("TILER_SL16_MODE", "0"),
-                      "shortlist_ms": ms, "tier2_queries": st["fallback_queries"], "tier3_queries": st["exhaustive_queries"],
+    print(json.dumps({"tag": args.tag, "gate": args.gate, "shortlist_ms": ms, "tier2_queries": st["fallback_queries"], "tier3_queries": st["exhaustive_queries"],
                       "candidates": m0, "flat_queries": st["flat_queries"],
                       "frac": round(flops / (best * 1e-3) / 1e12 / 2500.0, 4), "digest": h.hexdigest()[:16]}),
           flush=True)

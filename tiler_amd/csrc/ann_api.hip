@@ -1187,51 +1187,8 @@ int tiler_psyv_batch(int n, const int32_t *rgb, int n_tiles, const uint8_t *palp
                      int n_palettes, const int32_t *palettes, const int32_t *pal_of, const uint8_t *flags_per,
                      int flags, int gamma, double *out64, float *out32) {
     if (!ensure_init()) return -1;
-    if (n < 0) {
-        set_error("psyv: n < 0");
-        return -1;
-    }
-    if (n == 0) return 0;
-    const bool from_pal = (flags & 1) != 0 || (flags_per != nullptr);
-    std::vector<void *> bufs;
-    auto up = [&](const void *h, size_t bytes) -> void * {
-        if (!h || bytes == 0) return nullptr;
-        void *d = nullptr;
-        if (hipMalloc(&d, bytes) != hipSuccess) return nullptr;
-        bufs.push_back(d);
-        hipMemcpy(d, h, bytes, hipMemcpyHostToDevice);
-        return d;
-    };
-    auto cleanup = [&]() {
-        for (void *p : bufs) hipFree(p);
-    };
-    int32_t *d_rgb = (int32_t *)up(rgb, rgb ? (size_t)n * 64 * 4 : 0);
-    uint8_t *d_pp = from_pal ? (uint8_t *)up(palpix, (size_t)std::max(n_tiles, 0) * 64) : nullptr;
-    int32_t *d_to = (int32_t *)up(tile_of, tile_of ? (size_t)n * 4 : 0);
-    int32_t *d_pal = from_pal ? (int32_t *)up(palettes, (size_t)std::max(n_palettes, 0) * 16 * 4) : nullptr;
-    int32_t *d_po = (int32_t *)up(pal_of, pal_of ? (size_t)n * 4 : 0);
-    uint8_t *d_fp = (uint8_t *)up(flags_per, flags_per ? (size_t)n : 0);
-    double *d_o64 = nullptr;
-    float *d_o32 = nullptr;
-    if (out64 && hipMalloc((void **)&d_o64, (size_t)n * 192 * 8) == hipSuccess) bufs.push_back(d_o64);
-    if (out32 && hipMalloc((void **)&d_o32, (size_t)n * 192 * 4) == hipSuccess) bufs.push_back(d_o32);
-    if ((!rgb && !from_pal) || (rgb && !d_rgb) || (from_pal && (!d_pp || !d_pal)) || (out64 && !d_o64) ||
-        (out32 && !d_o32)) {
-        cleanup();
-        set_error("psyv: missing input buffer or device allocation failed");
-        return -1;
-    }
-    int rc = tiler_psyv_batch_dev(n, d_rgb, d_pp, d_to, d_pal, d_po, d_fp, flags, gamma, d_o64, d_o32, nullptr);
-    if (rc == 0) {
-        if (out64) hipMemcpy(out64, d_o64, (size_t)n * 192 * 8, hipMemcpyDeviceToHost);
-        if (out32) hipMemcpy(out32, d_o32, (size_t)n * 192 * 4, hipMemcpyDeviceToHost);
-        if (hipDeviceSynchronize() != hipSuccess) {
-            set_error("psyv: kernel failed");
-            rc = -1;
-        }
-    }
-    cleanup();
-    return rc;
+    return psyv_batch_host(n, rgb, n_tiles, palpix, tile_of, n_palettes, palettes, pal_of, flags_per, flags, gamma, out64,
+                           out32);
 }
 
 static int set_maps_one(ann_kdtree *t, const int32_t *tr_tile, const int32_t *tr_pal, const uint8_t *tr_attr) {
@@ -1438,64 +1395,14 @@ int tiler_prepare_dither_tiles_dev(long n_tiles, const int32_t *d_rgb, int n_pal
 int tiler_prepare_dither_tiles(long n_tiles, const int32_t *rgb, int n_palettes, int gamma, int use_wavelets,
                                int max_iter, uint32_t seed, int32_t *labels, double *centroids, int *iterations) {
     if (!ensure_init()) return -1;
-    if (n_tiles < 0 || n_palettes <= 0 || (n_tiles > 0 && (!rgb || !labels)) || !centroids) {
-        set_error("prepare_dither_tiles: invalid arguments");
-        return -1;
-    }
-    const size_t b_rgb = (size_t)n_tiles * 256, b_lab = (size_t)n_tiles * 4, b_c = (size_t)n_palettes * 192 * 8;
-    char *buf = nullptr;
-    TILER_HIP_CHECK(hipMalloc((void **)&buf, b_rgb + b_lab + b_c + 512));
-    char *d_rgb = buf, *d_lab = buf + ((b_rgb + 255) & ~(size_t)255), *d_c = d_lab + ((b_lab + 255) & ~(size_t)255);
-    hipStream_t st = nullptr;
-    int rc = -1;
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess) {
-        do {
-            if (n_tiles > 0 && hipMemcpyAsync(d_rgb, rgb, b_rgb, hipMemcpyHostToDevice, st) != hipSuccess) break;
-            if (prepare_dither_dev(n_tiles, (const int32_t *)d_rgb, n_palettes, gamma, use_wavelets,
-                                   max_iter <= 0 ? 0x7fffffff : max_iter, seed, (int32_t *)d_lab, (double *)d_c,
-                                   iterations, st))
-                break;
-            if (n_tiles > 0 && hipMemcpyAsync(labels, d_lab, b_lab, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-            if (hipMemcpyAsync(centroids, d_c, b_c, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-            if (hipStreamSynchronize(st) != hipSuccess) break;
-            rc = 0;
-        } while (0);
-        (void)hipStreamDestroy(st);
-    }
-    if (rc && !last_error()[0]) set_error("prepare_dither_tiles: HIP failure");
-    (void)hipFree(buf);
-    return rc;
+    return prepare_dither_host(n_tiles, rgb, n_palettes, gamma, use_wavelets, max_iter <= 0 ? 0x7fffffff : max_iter, seed,
+                               labels, centroids, iterations);
 }
 
 int tiler_kmeans(const double *X, long n, int d, int k, int max_iter, uint32_t seed, int32_t *labels,
                  double *centroids, int *iterations) {
     if (!ensure_init()) return -1;
-    if (n <= 0 || d <= 0 || d > 192 || k <= 0 || !X || !labels || !centroids) {
-        set_error("kmeans: invalid arguments");
-        return -1;
-    }
-    const size_t bx = (size_t)n * d * 8, bl = (size_t)n * 4, bc = (size_t)k * d * 8;
-    char *buf = nullptr;
-    TILER_HIP_CHECK(hipMalloc((void **)&buf, bx + bl + bc + 512));
-    char *d_x = buf, *d_l = buf + ((bx + 255) & ~(size_t)255), *d_c = d_l + ((bl + 255) & ~(size_t)255);
-    hipStream_t st = nullptr;
-    int rc = -1;
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess) {
-        do {
-            if (hipMemcpyAsync(d_x, X, bx, hipMemcpyHostToDevice, st) != hipSuccess) break;
-            if (kmeans_dev((const double *)d_x, n, d, k, max_iter <= 0 ? 0x7fffffff : max_iter, seed, (int32_t *)d_l,
-                           (double *)d_c, iterations, st))
-                break;
-            if (hipMemcpyAsync(labels, d_l, bl, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-            if (hipMemcpyAsync(centroids, d_c, bc, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-            if (hipStreamSynchronize(st) != hipSuccess) break;
-            rc = 0;
-        } while (0);
-        (void)hipStreamDestroy(st);
-    }
-    if (rc && !last_error()[0]) set_error("kmeans: HIP failure");
-    (void)hipFree(buf);
-    return rc;
+    return kmeans_host(X, n, d, k, max_iter <= 0 ? 0x7fffffff : max_iter, seed, labels, centroids, iterations);
 }
 
 int tiler_finish_quantize_order(int n_palettes, const int32_t *use_count, int32_t *lut) {

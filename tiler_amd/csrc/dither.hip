@@ -15,6 +15,7 @@
 #include <string>
 
 #include "dither.hpp"
+#include "stage.hpp"
 
 namespace tiler {
 
@@ -395,34 +396,13 @@ int dither_tiles_host(int n, const int32_t *rgb, const int32_t *pal_of, const in
             return -1;
         }
     if (n == 0) return 0;
-    const size_t b_rgb = (size_t)n * 256, b_po = (size_t)n * 4, b_pal = (size_t)n_palettes * palsize * 4;
-    const size_t b_px = (size_t)n * 64;
-    char *buf = nullptr;
-    TILER_HIP_CHECK(hipMalloc((void **)&buf, b_rgb + b_po + b_pal + b_px + 2 * (size_t)n + 64));
-    int32_t *d_rgb = (int32_t *)buf, *d_po = (int32_t *)(buf + b_rgb), *d_pal = (int32_t *)(buf + b_rgb + b_po);
-    uint8_t *d_px = (uint8_t *)(buf + b_rgb + b_po + b_pal), *d_hm = d_px + b_px, *d_vm = d_hm + n;
-    hipStream_t st = nullptr;
-    int rc = -1;
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
-        (void)hipFree(buf);
-        set_error("dither: stream creation failed");
+    HostStage s("dither");
+    const int32_t *d_rgb = s.in(rgb, (size_t)n * 64), *d_po = s.in(pal_of, (size_t)n);
+    const int32_t *d_pal = s.in(palettes, (size_t)n_palettes * palsize);
+    uint8_t *d_px = s.out(palpix, (size_t)n * 64), *d_hm = s.out(hm, (size_t)n), *d_vm = s.out(vm, (size_t)n);
+    if (!s.ok() || dither_tiles_dev(n, d_rgb, d_po, d_pal, n_palettes, palsize, mixed, d_px, d_hm, d_vm, s.stream()))
         return -1;
-    }
-    do {
-        if (hipMemcpyAsync(d_rgb, rgb, b_rgb, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (hipMemcpyAsync(d_po, pal_of, b_po, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (hipMemcpyAsync(d_pal, palettes, b_pal, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (dither_tiles_dev(n, d_rgb, d_po, d_pal, n_palettes, palsize, mixed, d_px, d_hm, d_vm, st)) break;
-        if (hipMemcpyAsync(palpix, d_px, b_px, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-        if (hipMemcpyAsync(hm, d_hm, n, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-        if (hipMemcpyAsync(vm, d_vm, n, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-        if (hipStreamSynchronize(st) != hipSuccess) break;
-        rc = 0;
-    } while (0);
-    if (rc) set_error(std::string("dither: HIP failure: ") + hipGetErrorString(hipGetLastError()));
-    (void)hipStreamDestroy(st);
-    (void)hipFree(buf);
-    return rc;
+    return s.finish();
 }
 
 }  // namespace tiler

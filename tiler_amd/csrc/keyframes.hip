@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "keyframes.hpp"
+#include "stage.hpp"
 
 namespace tiler {
 
@@ -259,23 +260,10 @@ int interframe_corr_host(const int32_t *rgb, int F, int tm_w, int tm_h, double *
         return -1;
     }
     if (F <= 1) return 0;
-    const size_t bytes = (size_t)F * tm_w * tm_h * 64 * 4;
-    int32_t *d = nullptr;
-    hipStream_t st = nullptr;
-    TILER_HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    int rc = -1;
-    if (hipMalloc((void **)&d, bytes) == hipSuccess) {
-        if (hipMemcpyAsync(d, rgb, bytes, hipMemcpyHostToDevice, st) == hipSuccess)
-            rc = interframe_corr_dev(d, F, tm_w, tm_h, corr, st);
-        else
-            set_error("keyframes: host-to-device copy failed");
-        (void)hipStreamSynchronize(st);
-        (void)hipFree(d);
-    } else {
-        set_error("keyframes: device allocation failed");
-    }
-    (void)hipStreamDestroy(st);
-    return rc;
+    HostStage s("keyframes");
+    const int32_t *d_rgb = s.in(rgb, (size_t)F * tm_w * tm_h * 64);
+    if (!s.ok() || interframe_corr_dev(d_rgb, F, tm_w, tm_h, corr, s.stream())) return -1;
+    return s.finish();
 }
 
 // btnLoadClick main.pas:1099-1146: the shot-transition split over the correlations (host bookkeeping).

@@ -23,7 +23,7 @@
 
 #include "kmeans.hpp"
 #include "psyv.hpp"
-#include "tiler_common.hpp"
+#include "stage.hpp"
 
 #pragma clang fp contract(off)
 
@@ -422,6 +422,36 @@ int prepare_dither_dev(long n_tiles, const int32_t *d_rgb, int P, int gamma, int
     (void)hipStreamSynchronize(stream);
     (void)hipFree(X);
     return rc;
+}
+
+// host-buffer forms
+int kmeans_host(const double *X, long n, int d, int k, int max_iter, uint32_t seed, int32_t *labels, double *centroids,
+                int *iterations) {
+    if (n <= 0 || d <= 0 || d > 192 || k <= 0 || !X || !labels || !centroids) {
+        set_error("kmeans: invalid arguments");
+        return -1;
+    }
+    HostStage s("kmeans");
+    const double *d_X = s.in(X, (size_t)n * d);
+    int32_t *d_l = s.out(labels, (size_t)n);
+    double *d_c = s.out(centroids, (size_t)k * d);
+    if (!s.ok() || kmeans_dev(d_X, n, d, k, max_iter, seed, d_l, d_c, iterations, s.stream())) return -1;
+    return s.finish();
+}
+
+int prepare_dither_host(long n_tiles, const int32_t *rgb, int P, int gamma, int use_wavelets, int max_iter,
+                        uint32_t seed, int32_t *labels, double *centroids, int *iterations) {
+    if (n_tiles < 0 || P <= 0 || (n_tiles > 0 && (!rgb || !labels)) || !centroids) {
+        set_error("prepare_dither_tiles: invalid arguments");
+        return -1;
+    }
+    HostStage s("prepare_dither_tiles");
+    const int32_t *d_rgb = s.in(rgb, (size_t)n_tiles * 64);
+    int32_t *d_l = s.out(labels, (size_t)n_tiles);
+    double *d_c = s.out(centroids, (size_t)P * 192);
+    if (!s.ok() || prepare_dither_dev(n_tiles, d_rgb, P, gamma, use_wavelets, max_iter, seed, d_l, d_c, iterations, s.stream()))
+        return -1;
+    return s.finish();
 }
 
 }  // namespace tiler

@@ -14,4 +14,10 @@ int kmeans_dev(const double *d_X, long n, int d, int k, int max_iter, uint32_t s
 int prepare_dither_dev(long n_tiles, const int32_t *d_rgb, int P, int gamma, int use_wavelets, int max_iter,
                        uint32_t seed, int32_t *d_labels, double *d_cent, int *iterations, hipStream_t stream);
 
+// host-buffer forms of the two (tiler_kmeans, tiler_prepare_dither_tiles)
+int kmeans_host(const double *X, long n, int d, int k, int max_iter, uint32_t seed, int32_t *labels, double *centroids,
+                int *iterations);
+int prepare_dither_host(long n_tiles, const int32_t *rgb, int P, int gamma, int use_wavelets, int max_iter,
+                        uint32_t seed, int32_t *labels, double *centroids, int *iterations);
+
 }  // namespace tiler

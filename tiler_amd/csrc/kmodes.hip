@@ -29,6 +29,7 @@
 
 #include "kmodes.hpp"
 #include "kmodes_dev.hpp"
+#include "stage.hpp"
 
 namespace tiler {
 
@@ -1728,40 +1729,7 @@ int kmodes_medoids_batch_dev(const uint8_t *d_X, const int32_t *h_boff, int nb, 
     return rc;
 }
 
-// host-buffer entry points: stage through a private stream
-template <class F>
-static int with_host_batch(const uint8_t *X, long N, long K, int32_t *labels_out, uint8_t *cent_out, F run) {
-    uint8_t *d_X = nullptr, *d_c = nullptr;
-    int32_t *d_l = nullptr;
-    hipStream_t st = nullptr;
-    TILER_HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    int rc = -1;
-    do {
-        if (hipMalloc((void **)&d_X, (size_t)std::max(N, 1L) * KM_A) != hipSuccess) break;
-        if (hipMalloc((void **)&d_c, (size_t)std::max(K, 1L) * KM_A) != hipSuccess) break;
-        if (hipMalloc((void **)&d_l, (size_t)std::max(N, 1L) * 4) != hipSuccess) break;
-        if (N > 0 && hipMemcpyAsync(d_X, X, (size_t)N * KM_A, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (!labels_out && !cent_out) {  // medoids: labels/centroids are inputs, results go to host in run()
-            rc = run(d_X, d_l, d_c, st) ? -2 : 0;
-            break;
-        }
-        if (run(d_X, d_l, d_c, st)) {
-            rc = -2;
-            break;
-        }
-        if (hipMemcpyAsync(labels_out, d_l, (size_t)N * 4, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-        if (hipMemcpyAsync(cent_out, d_c, (size_t)K * KM_A, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-        if (hipStreamSynchronize(st) != hipSuccess) break;
-        rc = 0;
-    } while (0);
-    if (rc == -1) set_error("kmodes: HIP failure");
-    (void)hipFree(d_X);
-    (void)hipFree(d_c);
-    (void)hipFree(d_l);
-    (void)hipStreamDestroy(st);
-    return rc < 0 ? -1 : 0;
-}
-
+// host-buffer entry points
 int kmodes_batch_host(const uint8_t *X, const int32_t *boff, int nb, const int32_t *k, const int32_t *start,
                       int n_modalities, int32_t *labels, uint8_t *centroids, int32_t *n_iter, uint64_t *cost) {
     if (!X || !boff || nb <= 0 || !k || !start || !labels || !centroids) {
@@ -1770,9 +1738,12 @@ int kmodes_batch_host(const uint8_t *X, const int32_t *boff, int nb, const int32
     }
     long K = 0;
     for (int b = 0; b < nb; b++) K += k[b];
-    return with_host_batch(X, boff[nb], K, labels, centroids, [&](uint8_t *dX, int32_t *dl, uint8_t *dc, hipStream_t st) {
-        return kmodes_batch_dev(dX, boff, nb, k, start, n_modalities, dl, dc, n_iter, cost, st);
-    });
+    HostStage s("kmodes");
+    const uint8_t *d_X = s.in(X, (size_t)boff[nb] * KM_A);
+    int32_t *d_l = s.out(labels, (size_t)boff[nb]);
+    uint8_t *d_c = s.out(centroids, (size_t)K * KM_A);
+    if (!s.ok() || kmodes_batch_dev(d_X, boff, nb, k, start, n_modalities, d_l, d_c, n_iter, cost, s.stream())) return -1;
+    return s.finish();
 }
 
 int kmodes_medoids_batch_host(const uint8_t *X, const int32_t *boff, int nb, const int32_t *k, const int32_t *labels,
@@ -1789,11 +1760,11 @@ int kmodes_medoids_batch_host(const uint8_t *X, const int32_t *boff, int nb, con
                 set_error("kmodes_medoids: label out of range");
                 return -1;
             }
-    return with_host_batch(X, boff[nb], K, nullptr, nullptr, [&](uint8_t *dX, int32_t *dl, uint8_t *dc, hipStream_t st) {
-        TILER_HIP_CHECK(hipMemcpyAsync(dl, labels, (size_t)boff[nb] * 4, hipMemcpyHostToDevice, st));
-        TILER_HIP_CHECK(hipMemcpyAsync(dc, centroids, (size_t)K * KM_A, hipMemcpyHostToDevice, st));
-        return kmodes_medoids_batch_dev(dX, boff, nb, k, dl, dc, medoid, counts, st);
-    });
+    HostStage s("kmodes_medoids");
+    const uint8_t *d_X = s.in(X, (size_t)boff[nb] * KM_A), *d_c = s.in(centroids, (size_t)K * KM_A);
+    const int32_t *d_l = s.in(labels, (size_t)boff[nb]);
+    if (!s.ok() || kmodes_medoids_batch_dev(d_X, boff, nb, k, d_l, d_c, medoid, counts, s.stream())) return -1;
+    return s.finish();
 }
 
 int kmodes_medoids_host(const uint8_t *X, int n, const int32_t *labels, const uint8_t *centroids, int k,

@@ -28,7 +28,7 @@
 #include <vector>
 
 #include "palette.hpp"
-#include "tiler_common.hpp"
+#include "stage.hpp"
 
 namespace tiler {
 
@@ -930,29 +930,12 @@ int quantize_palettes_host(long n_tiles, const int32_t *rgb, const int32_t *pal_
         set_error("quantize_palettes: invalid arguments");
         return -1;
     }
-    const size_t b_rgb = (size_t)n_tiles * 256, b_po = (size_t)n_tiles * 4, b_act = active ? (size_t)n_tiles : 0;
-    char *buf = nullptr;
-    TILER_HIP_CHECK(hipMalloc((void **)&buf, b_rgb + b_po + b_act + 64));
-    hipStream_t st = nullptr;
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
-        (void)hipFree(buf);
-        set_error("quantize_palettes: stream creation failed");
+    HostStage s("quantize_palettes");
+    const int32_t *d_rgb = s.in(rgb, (size_t)n_tiles * 64), *d_po = s.in(pal_of, (size_t)n_tiles);
+    const uint8_t *d_act = s.in(active, (size_t)n_tiles);
+    if (!s.ok() || quantize_palettes_dev(n_tiles, d_rgb, d_po, d_act, P, palsize, bpc, pal_out, use_count, hist, s.stream()))
         return -1;
-    }
-    int rc = -1;
-    do {
-        if (hipMemcpyAsync(buf, rgb, b_rgb, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (hipMemcpyAsync(buf + b_rgb, pal_of, b_po, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (active && hipMemcpyAsync(buf + b_rgb + b_po, active, b_act, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        rc = quantize_palettes_dev(n_tiles, (const int32_t *)buf, (const int32_t *)(buf + b_rgb),
-                                   active ? (const uint8_t *)(buf + b_rgb + b_po) : nullptr, P, palsize, bpc, pal_out,
-                                   use_count, hist, st);
-    } while (0);
-    if (rc && !last_error()[0]) set_error("quantize_palettes: HIP copy failed");
-    (void)hipStreamSynchronize(st);
-    (void)hipStreamDestroy(st);
-    (void)hipFree(buf);
-    return rc;
+    return s.finish();
 }
 
 }  // namespace tiler

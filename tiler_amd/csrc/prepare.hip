@@ -289,7 +289,8 @@ NNIndex *prepare_frame_tiling_dev(NNIndex *global, PrepScratch &s, const int32_t
     pa.gamma = gamma;
     pa.out32 = rows;
     if (M > 0 && launch_psyv(pa, stream)) {
-        hipFree(rows);
+        (void)hipStreamSynchronize(stream);  // dfree's rule: nothing queued still uses the block
+        dfree(rows);
         return nullptr;
     }
     NNIndex *ix = nn_index_create_dev(rows, (int)M, 192, 1, KD_SPLIT_STD, stream);  // owns rows

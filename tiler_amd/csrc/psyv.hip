@@ -9,6 +9,7 @@
 // HBM traffic per tile: 256 B in (RGB) or 64 B + 64 B palette, 768 B (fp32) / 1536 B (fp64) out.
 #include "psyv.hpp"
 #include "psyv_dev.hpp"
+#include "stage.hpp"
 
 #pragma clang fp contract(off)
 
@@ -216,6 +217,38 @@ int launch_psyv(PsyvArgs args, hipStream_t stream) {
     }
     TILER_HIP_CHECK(hipGetLastError());
     return 0;
+}
+
+int psyv_batch_host(int n, const int32_t *rgb, int n_tiles, const uint8_t *palpix, const int32_t *tile_of,
+                    int n_palettes, const int32_t *palettes, const int32_t *pal_of, const uint8_t *flags_per, int flags,
+                    int gamma, double *out64, float *out32) {
+    if (n < 0) {
+        set_error("psyv: n < 0");
+        return -1;
+    }
+    if (n == 0) return 0;
+    const bool from_pal = (flags & PSYV_FROM_PAL) != 0 || (flags_per != nullptr);
+    if ((!rgb && !from_pal) || (from_pal && (!palpix || n_tiles <= 0 || !palettes || n_palettes <= 0))) {
+        set_error("psyv: missing input buffer");
+        return -1;
+    }
+    HostStage s("psyv");
+    PsyvArgs a;
+    a.n = n;
+    a.rgb = s.in(rgb, (size_t)n * 64);
+    if (from_pal) {
+        a.palpix = s.in(palpix, (size_t)n_tiles * 64);
+        a.palettes = s.in(palettes, (size_t)n_palettes * 16);
+    }
+    a.tile_of = s.in(tile_of, (size_t)n);
+    a.pal_of = s.in(pal_of, (size_t)n);
+    a.flags_per = s.in(flags_per, (size_t)n);
+    a.flags = flags;
+    a.gamma = gamma;
+    a.out64 = s.out(out64, (size_t)n * 192);
+    a.out32 = s.out(out32, (size_t)n * 192);
+    if (!s.ok() || launch_psyv(a, s.stream())) return -1;
+    return s.finish();
 }
 
 }  // namespace tiler

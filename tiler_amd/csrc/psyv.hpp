@@ -32,4 +32,10 @@ struct PsyvArgs {
 
 int launch_psyv(PsyvArgs args, hipStream_t stream);
 
+// host-buffer form (tiler_psyv_batch): palpix [n_tiles][64] and palettes [n_palettes][16] are read only when the
+// descriptors come from palettes (PSYV_FROM_PAL or flags_per); out64 / out32: either or both
+int psyv_batch_host(int n, const int32_t *rgb, int n_tiles, const uint8_t *palpix, const int32_t *tile_of,
+                    int n_palettes, const int32_t *palettes, const int32_t *pal_of, const uint8_t *flags_per, int flags,
+                    int gamma, double *out64, float *out32);
+
 }  // namespace tiler

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "quality.hpp"
+#include "stage.hpp"
 
 namespace tiler {
 
@@ -128,67 +129,20 @@ int render_frames_host(int F, int Q, const int32_t *tile, const int32_t *pal, co
     }
     if (F == 0) return 0;
     const size_t n = (size_t)F * Q;
-    const bool has_sm = smoothed != nullptr;
-    // one allocation, every array at a 256-byte boundary
-    struct Part {
-        const void *src;
-        size_t bytes, off;
-    } parts[] = {{tile, n * 4, 0},          {pal, n * 4, 0},
-                 {hm, n, 0},                {vm, n, 0},
-                 {sm_tile, has_sm ? n * 4 : 0, 0}, {sm_pal, has_sm ? n * 4 : 0, 0},
-                 {sm_hm, has_sm ? n : 0, 0},       {sm_vm, has_sm ? n : 0, 0},
-                 {smoothed, has_sm ? n : 0, 0},    {palpix, (size_t)T * 64, 0},
-                 {thm, (size_t)T, 0},       {tvm, (size_t)T, 0},
-                 {palettes, (size_t)n_rows * palsize * 4, 0}, {pal_row0, (size_t)F * 4, 0}};
-    constexpr int NP = sizeof(parts) / sizeof(parts[0]);
-    size_t total = 0;
-    for (int i = 0; i < NP; i++) {
-        parts[i].off = total;
-        total += (parts[i].bytes + 255) & ~(size_t)255;
-    }
-    const size_t off_out = total, off_inv = off_out + ((n * 256 + 255) & ~(size_t)255);
-    total = off_inv + (((size_t)F * 4 + 255) & ~(size_t)255);
-    char *buf = nullptr;
-    hipStream_t st = nullptr;
-    TILER_HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    int rc = -1;
-    if (hipMalloc((void **)&buf, total) == hipSuccess) {
-        do {
-            bool copied = true;
-            for (int i = 0; i < NP && copied; i++)
-                if (parts[i].bytes && hipMemcpyAsync(buf + parts[i].off, parts[i].src, parts[i].bytes,
-                                                     hipMemcpyHostToDevice, st) != hipSuccess)
-                    copied = false;
-            if (!copied) {
-                set_error("render: host-to-device copy failed");
-                break;
-            }
-            auto at = [&](int i) -> void * { return parts[i].bytes ? buf + parts[i].off : nullptr; };
-            // empty tile / palette tables keep a valid (never read) address
-            if (render_frames_dev(F, Q, (const int32_t *)at(0), (const int32_t *)at(1), (const uint8_t *)at(2),
-                                  (const uint8_t *)at(3), (const int32_t *)at(4), (const int32_t *)at(5),
-                                  (const uint8_t *)at(6), (const uint8_t *)at(7), (const uint8_t *)at(8), T,
-                                  (const uint8_t *)(buf + parts[9].off), (const uint8_t *)(buf + parts[10].off),
-                                  (const uint8_t *)(buf + parts[11].off), n_rows, palsize,
-                                  (const int32_t *)(buf + parts[12].off), (const int32_t *)at(13), n_palettes,
-                                  (int32_t *)(buf + off_out), (int32_t *)(buf + off_inv), st))
-                break;
-            if (hipMemcpyAsync(out_rgb, buf + off_out, n * 256, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                (invalid &&
-                 hipMemcpyAsync(invalid, buf + off_inv, (size_t)F * 4, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-                hipStreamSynchronize(st) != hipSuccess) {
-                set_error("render: device-to-host copy failed");
-                break;
-            }
-            rc = 0;
-        } while (0);
-        (void)hipStreamSynchronize(st);
-        (void)hipFree(buf);
-    } else {
-        set_error("render: device allocation failed");
-    }
-    (void)hipStreamDestroy(st);
-    return rc;
+    HostStage s("render");
+    const int32_t *d_tile = s.in(tile, n), *d_pal = s.in(pal, n);
+    const uint8_t *d_hm = s.in(hm, n), *d_vm = s.in(vm, n);
+    const int32_t *d_sm_tile = s.in(sm_tile, n), *d_sm_pal = s.in(sm_pal, n);
+    const uint8_t *d_sm_hm = s.in(sm_hm, n), *d_sm_vm = s.in(sm_vm, n), *d_smoothed = s.in(smoothed, n);
+    // empty tile / palette tables keep a valid (never read) address
+    const uint8_t *d_palpix = s.in(palpix, (size_t)T * 64), *d_thm = s.in(thm, (size_t)T), *d_tvm = s.in(tvm, (size_t)T);
+    const int32_t *d_palettes = s.in(palettes, (size_t)n_rows * palsize), *d_row0 = s.in(pal_row0, (size_t)F);
+    int32_t *d_out = s.out(out_rgb, n * 64), *d_invalid = s.out(invalid, (size_t)F);
+    if (!s.ok() || render_frames_dev(F, Q, d_tile, d_pal, d_hm, d_vm, d_sm_tile, d_sm_pal, d_sm_hm, d_sm_vm, d_smoothed, T,
+                                     d_palpix, d_thm, d_tvm, n_rows, palsize, d_palettes, d_row0, n_palettes, d_out,
+                                     d_invalid, s.stream()))
+        return -1;
+    return s.finish();
 }
 
 // ---- Quality --------------------------------------------------------------------------------------------------
@@ -439,24 +393,11 @@ int frame_quality_host(const int32_t *src, const int32_t *dst, int F, int tm_w, 
         return -1;
     }
     if (F == 0) return 0;
-    const size_t bytes = (size_t)F * tm_w * tm_h * 64 * 4;  // a multiple of 256: the second frame set stays aligned
-    char *d = nullptr;
-    hipStream_t st = nullptr;
-    TILER_HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    int rc = -1;
-    if (hipMalloc((void **)&d, 2 * bytes) == hipSuccess) {
-        if (hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, st) == hipSuccess &&
-            hipMemcpyAsync(d + bytes, dst, bytes, hipMemcpyHostToDevice, st) == hipSuccess)
-            rc = frame_quality_dev((const int32_t *)d, (const int32_t *)(d + bytes), F, tm_w, tm_h, corr, sse, st);
-        else
-            set_error("quality: host-to-device copy failed");
-        (void)hipStreamSynchronize(st);
-        (void)hipFree(d);
-    } else {
-        set_error("quality: device allocation failed");
-    }
-    (void)hipStreamDestroy(st);
-    return rc;
+    const size_t n = (size_t)F * tm_w * tm_h * 64;
+    HostStage s("quality");
+    const int32_t *d_src = s.in(src, n), *d_dst = s.in(dst, n);
+    if (!s.ok() || frame_quality_dev(d_src, d_dst, F, tm_w, tm_h, corr, sse, s.stream())) return -1;
+    return s.finish();
 }
 
 }  // namespace tiler

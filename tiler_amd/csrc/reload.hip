@@ -23,6 +23,7 @@
 
 #include "kmodes_dev.hpp"
 #include "reload.hpp"
+#include "stage.hpp"
 
 namespace tiler {
 
@@ -332,29 +333,6 @@ namespace {
 
 unsigned grid_for(long n, long cap = 8192) { return (unsigned)std::max<long>(1, std::min<long>(cap, (n + RL_NT - 1) / RL_NT)); }
 
-// device blocks of one call: the stream is drained before they go back to the cache (dfree's rule)
-struct Blocks {
-    hipStream_t st;
-    std::vector<void *> p;
-    explicit Blocks(hipStream_t s) : st(s) {}
-    ~Blocks() {
-        if (p.empty()) return;
-        (void)hipStreamSynchronize(st);
-        for (void *b : p) dfree(b);
-    }
-    template <class T>
-    bool get(T *&out, size_t bytes) {
-        void *b = nullptr;
-        if (dmalloc(&b, std::max<size_t>(bytes, 256)) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        p.push_back(b);
-        out = (T *)b;
-        return true;
-    }
-};
-
 struct RowSet {
     const uint8_t *rows;  // [R][80]
     const uint4 *prep;    // [R][KM_PW / 4]
@@ -659,46 +637,20 @@ int min_dissim_groups_dev(const uint8_t *d_rows, long n, const int32_t *grp_off,
     return 0;
 }
 
-// ---- host-buffer forms: staged through a stream of the pool ----
-namespace {
-struct PoolStream {
-    hipStream_t st = nullptr;
-    bool ok;
-    PoolStream() : ok(stream_get(&st) == hipSuccess) {}
-    ~PoolStream() {
-        if (ok) stream_put(st);
-    }
-};
-}  // namespace
-
+// ---- host-buffer forms ----
 int tileset_match_host(Tileset *ts, uint8_t *palpix, const uint8_t *active, long nt, int32_t *idx, uint64_t *dis) {
     if (!ts || nt < 0 || (nt > 0 && (!palpix || !active))) {
         set_error("tileset_match: invalid arguments");
         return -1;
     }
     if (nt == 0) return 0;
-    PoolStream ps;
-    if (!ps.ok) {
-        set_error("tileset_match: no stream");
-        return -1;
-    }
-    Blocks B(ps.st);
-    uint8_t *d_pix = nullptr, *d_act = nullptr;
-    int32_t *d_idx = nullptr;
-    uint64_t *d_dis = nullptr;
-    if (!B.get(d_pix, (size_t)nt * 64) || !B.get(d_act, (size_t)nt) || !B.get(d_idx, (size_t)nt * 4) ||
-        !B.get(d_dis, (size_t)nt * 8)) {
-        set_error("tileset_match: out of device memory");
-        return -1;
-    }
-    TILER_HIP_CHECK(hipMemcpyAsync(d_pix, palpix, (size_t)nt * 64, hipMemcpyHostToDevice, ps.st));
-    TILER_HIP_CHECK(hipMemcpyAsync(d_act, active, (size_t)nt, hipMemcpyHostToDevice, ps.st));
-    if (tileset_match_dev(ts, d_pix, d_act, nt, d_idx, d_dis, ps.st)) return -1;
-    TILER_HIP_CHECK(hipMemcpyAsync(palpix, d_pix, (size_t)nt * 64, hipMemcpyDeviceToHost, ps.st));
-    if (idx) TILER_HIP_CHECK(hipMemcpyAsync(idx, d_idx, (size_t)nt * 4, hipMemcpyDeviceToHost, ps.st));
-    if (dis) TILER_HIP_CHECK(hipMemcpyAsync(dis, d_dis, (size_t)nt * 8, hipMemcpyDeviceToHost, ps.st));
-    TILER_HIP_CHECK(hipStreamSynchronize(ps.st));
-    return 0;
+    HostStage s("tileset_match");
+    uint8_t *d_pix = s.inout(palpix, (size_t)nt * 64);
+    const uint8_t *d_act = s.in(active, (size_t)nt);
+    int32_t *d_idx = s.out(idx, (size_t)nt);
+    uint64_t *d_dis = s.out(dis, (size_t)nt);
+    if (!s.ok() || tileset_match_dev(ts, d_pix, d_act, nt, d_idx, d_dis, s.stream())) return -1;
+    return s.finish();
 }
 
 int min_dissim_groups_host(const uint8_t *rows, long n, const int32_t *grp_off, int ngroups, const uint8_t *items,
@@ -708,28 +660,14 @@ int min_dissim_groups_host(const uint8_t *rows, long n, const int32_t *grp_off, 
         return -1;
     }
     if (m == 0) return 0;
-    PoolStream ps;
-    if (!ps.ok) {
-        set_error("min_matching_dissim_groups: no stream");
+    HostStage s("min_matching_dissim_groups");
+    const uint8_t *d_rows = s.in(rows, (size_t)n * KM_A), *d_items = s.in(items, (size_t)m * KM_A);
+    const int32_t *d_grp = s.in(item_grp, (size_t)m);
+    int32_t *d_idx = s.out(idx, (size_t)m);
+    uint64_t *d_dis = s.out(dis, (size_t)m);
+    if (!s.ok() || min_dissim_groups_dev(d_rows, n, grp_off, ngroups, d_items, d_grp, m, d_idx, d_dis, s.stream()))
         return -1;
-    }
-    Blocks B(ps.st);
-    uint8_t *d_rows = nullptr, *d_items = nullptr;
-    int32_t *d_grp = nullptr, *d_idx = nullptr;
-    uint64_t *d_dis = nullptr;
-    if (!B.get(d_rows, (size_t)n * KM_A) || !B.get(d_items, (size_t)m * KM_A) || !B.get(d_grp, (size_t)m * 4) ||
-        !B.get(d_idx, (size_t)m * 4) || !B.get(d_dis, (size_t)m * 8)) {
-        set_error("min_matching_dissim_groups: out of device memory");
-        return -1;
-    }
-    if (n > 0) TILER_HIP_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)n * KM_A, hipMemcpyHostToDevice, ps.st));
-    TILER_HIP_CHECK(hipMemcpyAsync(d_items, items, (size_t)m * KM_A, hipMemcpyHostToDevice, ps.st));
-    TILER_HIP_CHECK(hipMemcpyAsync(d_grp, item_grp, (size_t)m * 4, hipMemcpyHostToDevice, ps.st));
-    if (min_dissim_groups_dev(d_rows, n, grp_off, ngroups, d_items, d_grp, m, d_idx, d_dis, ps.st)) return -1;
-    if (idx) TILER_HIP_CHECK(hipMemcpyAsync(idx, d_idx, (size_t)m * 4, hipMemcpyDeviceToHost, ps.st));
-    if (dis) TILER_HIP_CHECK(hipMemcpyAsync(dis, d_dis, (size_t)m * 8, hipMemcpyDeviceToHost, ps.st));
-    TILER_HIP_CHECK(hipStreamSynchronize(ps.st));
-    return 0;
+    return s.finish();
 }
 
 int reload_debug(long chunk, int qpt, int slices) {

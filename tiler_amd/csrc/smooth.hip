@@ -18,6 +18,7 @@
 #include "psyv.hpp"
 #include "psyv_dev.hpp"
 #include "smooth.hpp"
+#include "stage.hpp"
 
 #pragma clang fp contract(off)
 
@@ -311,46 +312,14 @@ int smooth_keyframe_host(int F, int Q, int32_t *tile, int32_t *tmpidx, int32_t *
             set_error("smooth: tile or palette index out of range");
             return -1;
         }
-    char *buf = nullptr;
-    const size_t sz_i = n * 4, sz_b = n;
-    const size_t total = 3 * sz_i + 3 * sz_b + (size_t)T * 64 + (size_t)P * 64 + 64;
-    TILER_HIP_CHECK(hipMalloc((void **)&buf, total));
-    int32_t *d_tile = (int32_t *)buf, *d_tmp = d_tile + n, *d_pal = d_tmp + n;
-    uint8_t *d_hm = (uint8_t *)(d_pal + n), *d_vm = d_hm + n, *d_sm = d_vm + n;
-    uint8_t *d_pp = d_sm + n;
-    int32_t *d_pals = (int32_t *)(((uintptr_t)(d_pp + (size_t)T * 64) + 15) & ~(uintptr_t)15);
-    hipStream_t st = nullptr;
-    int rc = -1;
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
-        hipFree(buf);
-        set_error("smooth: stream creation failed");
+    HostStage s("smooth");
+    int32_t *d_tile = s.inout(tile, n), *d_tmp = s.inout(tmpidx, n), *d_pal = s.inout(pal, n);
+    uint8_t *d_hm = s.inout(hm, n), *d_vm = s.inout(vm, n), *d_sm = s.inout(smoothed, n);
+    const uint8_t *d_pp = s.in(palpix, (size_t)T * 64);
+    const int32_t *d_pals = s.in(palettes, (size_t)P * 16);
+    if (!s.ok() || smooth_keyframe_dev(F, Q, d_tile, d_tmp, d_pal, d_hm, d_vm, d_sm, d_pp, d_pals, strength, s.stream()))
         return -1;
-    }
-    do {
-        if (hipMemcpyAsync(d_tile, tile, sz_i, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (tmpidx && hipMemcpyAsync(d_tmp, tmpidx, sz_i, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (hipMemcpyAsync(d_pal, pal, sz_i, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (hipMemcpyAsync(d_hm, hm, sz_b, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (hipMemcpyAsync(d_vm, vm, sz_b, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (hipMemcpyAsync(d_sm, smoothed, sz_b, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (hipMemcpyAsync(d_pp, palpix, (size_t)T * 64, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (hipMemcpyAsync(d_pals, palettes, (size_t)P * 64, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (smooth_keyframe_dev(F, Q, d_tile, tmpidx ? d_tmp : nullptr, d_pal, d_hm, d_vm, d_sm, d_pp, d_pals, strength,
-                                st))
-            break;
-        if (hipMemcpyAsync(tile, d_tile, sz_i, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-        if (tmpidx && hipMemcpyAsync(tmpidx, d_tmp, sz_i, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-        if (hipMemcpyAsync(pal, d_pal, sz_i, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-        if (hipMemcpyAsync(hm, d_hm, sz_b, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-        if (hipMemcpyAsync(vm, d_vm, sz_b, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-        if (hipMemcpyAsync(smoothed, d_sm, sz_b, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-        if (hipStreamSynchronize(st) != hipSuccess) break;
-        rc = 0;
-    } while (0);
-    if (rc) set_error(std::string("smooth: HIP failure: ") + last_error());
-    (void)hipStreamDestroy(st);
-    (void)hipFree(buf);
-    return rc;
+    return s.finish();
 }
 
 }  // namespace tiler

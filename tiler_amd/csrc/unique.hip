@@ -30,6 +30,7 @@
 #include <mutex>
 #include <vector>
 
+#include "stage.hpp"
 #include "unique.hpp"
 
 namespace tiler {
@@ -346,50 +347,12 @@ int make_tiles_unique_host(uint8_t *palpix, uint8_t *active, int64_t *use_count,
         set_error("make_tiles_unique: invalid arguments");
         return -1;
     }
-    hipStream_t st = nullptr;
-    if (stream_get(&st) != hipSuccess) {
-        set_error("make_tiles_unique: no stream");
-        return -1;
-    }
-    uint8_t *d_pix = nullptr, *d_act = nullptr;
-    int64_t *d_uc = nullptr, *d_mi = nullptr;
-    const size_t n = (size_t)std::max<long>(nt, 1);
-    int rc = -1;
-    do {
-        if (dmalloc((void **)&d_pix, n * 64) != hipSuccess || dmalloc((void **)&d_act, n) != hipSuccess ||
-            dmalloc((void **)&d_uc, n * 8) != hipSuccess || dmalloc((void **)&d_mi, n * 8) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("make_tiles_unique: out of device memory");
-            break;
-        }
-        auto copy = [&](void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
-            if (bytes == 0) return true;
-            const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, st);
-            if (e != hipSuccess) set_error(std::string("make_tiles_unique: copy: ") + hipGetErrorString(e));
-            return e == hipSuccess;
-        };
-        const size_t t = (size_t)nt;
-        if (!copy(d_pix, palpix, t * 64, hipMemcpyHostToDevice) || !copy(d_act, active, t, hipMemcpyHostToDevice) ||
-            !copy(d_uc, use_count, t * 8, hipMemcpyHostToDevice))
-            break;
-        if (make_tiles_unique_dev(d_pix, d_act, d_uc, d_mi, nt, seg_off, nseg, st)) break;
-        if (!copy(palpix, d_pix, t * 64, hipMemcpyDeviceToHost) || !copy(active, d_act, t, hipMemcpyDeviceToHost) ||
-            !copy(use_count, d_uc, t * 8, hipMemcpyDeviceToHost) ||
-            !copy(merge_index, d_mi, t * 8, hipMemcpyDeviceToHost))
-            break;
-        if (hipStreamSynchronize(st) != hipSuccess) {
-            set_error("make_tiles_unique: stream synchronisation failed");
-            break;
-        }
-        rc = 0;
-    } while (0);
-    (void)hipStreamSynchronize(st);  // the blocks go back to the cache idle (dfree's rule)
-    dfree(d_pix);
-    dfree(d_act);
-    dfree(d_uc);
-    dfree(d_mi);
-    stream_put(st);
-    return rc;
+    HostStage s("make_tiles_unique");
+    const size_t t = (size_t)nt;
+    uint8_t *d_pix = s.inout(palpix, t * 64), *d_act = s.inout(active, t);
+    int64_t *d_uc = s.inout(use_count, t), *d_mi = s.out(merge_index, t);
+    if (!s.ok() || make_tiles_unique_dev(d_pix, d_act, d_uc, d_mi, nt, seg_off, nseg, s.stream())) return -1;
+    return s.finish();
 }
 
 int unique_debug(int hash_bits) {

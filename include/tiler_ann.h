@@ -181,6 +181,10 @@ int tiler_psyv_batch(int n, const int32_t *rgb, int n_tiles, const uint8_t *palp
 int tiler_psyv_batch_dev(int n, const int32_t *rgb, const uint8_t *palpix, const int32_t *tile_of,
                          const int32_t *palettes, const int32_t *pal_of, const uint8_t *flags_per, int flags, int gamma,
                          double *out64, float *out32, void *stream);
+/* Test hook (process-wide): palette-mode DCT descriptors (no wavelets, no LAB, per-item flags absent or mirrors
+ * only) of min_items items or more are computed one lane per item, fewer one wave per item; 0 restores the default,
+ * 32768.  Results are identical for every value.  0 / -1 (min_items < 0). */
+int tiler_debug_psyv_lane_items(int64_t min_items);
 
 /* ---- FrameTiling (DoFrameTiling main.pas:3992-4047) ----
  * Attach the keyframe dataset's row -> (tile, palette, attrs) maps (TTilingDataset.TRTo*, main.pas:181-189)

@@ -50,8 +50,8 @@ def test_smooth_bit_exact(gpu, oracle, strength):
     pals = synth.palettes(rng, P)
     pals[1] = pals[0] + 1
     tile, pal, hm, vm = _tilemaps(rng, F, Q, T, P)
-    sm = np.zeros((F, Q), np.uint8)
     tmp = rng.integers(-1, 100, (F, Q)).astype(np.int32)
+    sm = rng.integers(0, 2, (F, Q)).astype(np.uint8)  # incoming flags: 'PrevTMI^ := TMI^' copies one into frame i-1
     g = smooth_keyframe(tile, pal, hm, vm, sm, palpix, pals, strength, tmpidx=tmp)
     o = oracle.smooth(tile, pal, hm, vm, sm, palpix, pals, strength, tmpidx=tmp)
     for a, b in zip(g, o):
@@ -59,6 +59,67 @@ def test_smooth_bit_exact(gpu, oracle, strength):
     changed = int(np.count_nonzero(g[0] != tile))
     if strength > 0:
         assert g[4].sum() > 0 and changed > 0  # both branches exercised
+
+
+def _twin_tileset(rng, T, P):
+    """T tiles whose upper half are one-pixel twins of the lower, P palettes of which the first two differ by a step."""
+    palpix = rng.integers(0, 16, (T, 64)).astype(np.uint8)
+    palpix[T // 2:] = palpix[:T // 2]
+    palpix[T // 2:, 5] = (palpix[T // 2:, 5] + 1) % 16
+    pals = synth.palettes(rng, P)
+    pals[1] = pals[0] + 1
+    return palpix, pals
+
+
+@pytest.mark.parametrize("with_tmpidx", [True, False], ids=["tmpidx", "no_tmpidx"])
+@pytest.mark.parametrize("F,Q", [(2, 1), (2, 7), (2, 8), (2, 9), (5, 3)])
+def test_smooth_small_shapes(gpu, oracle, F, Q, with_tmpidx):
+    """Fewer positions than one block of the chain kernel (8), exactly one block, one over, and the shortest chain
+    (F = 2): six seeded maps per shape, random incoming flags, all outputs equal to the restatement's; over the six
+    maps both a merge and a refusal occur."""
+    T, P = 40, 3
+    merged = kept = 0
+    for seed in range(6):
+        rng = np.random.default_rng(900 + 10 * F + Q + 100 * seed)
+        palpix, pals = _twin_tileset(rng, T, P)
+        tile, pal, hm, vm = _tilemaps(rng, F, Q, T, P, repeat=0.2)
+        sm = rng.integers(0, 2, (F, Q)).astype(np.uint8)
+        tmp = rng.integers(-1, 100, (F, Q)).astype(np.int32) if with_tmpidx else None
+        g = smooth_keyframe(tile, pal, hm, vm, sm, palpix, pals, 0.08, tmpidx=tmp)
+        o = oracle.smooth(tile, pal, hm, vm, sm, palpix, pals, 0.08, tmpidx=tmp)
+        for a, b in zip(g, o):
+            assert (a is None and b is None) or np.array_equal(a, b), seed
+        merged += int(g[4][1:].sum())
+        kept += int((g[4][1:] == 0).sum())
+    assert merged > 0 and kept > 0
+
+
+def test_smooth_per_item_mirrors_lane_per_item(gpu, oracle):
+    """The lane-per-item descriptor kernel with per-item mirrors (flags_per), through Smooth: threshold hook at 1, a
+    6-frame, 600-position map in which every position holds at least 2 distinct items and the items carry all four
+    mirror kinds."""
+    from tiler_amd import load
+    lib = load()
+    rng = np.random.default_rng(97)
+    F, Q, T, P = 6, 600, 120, 5
+    palpix, pals = _twin_tileset(rng, T, P)
+    tile, pal, hm, vm = _tilemaps(rng, F, Q, T, P, repeat=0.4)
+    same = np.all((tile == tile[0]) & (pal == pal[0]) & (hm == hm[0]) & (vm == vm[0]), axis=0)
+    hm[F - 1, same] ^= 1  # a static position: its last frame shows the other H mirror
+    keys = tile.astype(np.int64) * 64 + pal * 4 + hm * 2 + vm
+    assert all(np.unique(keys[:, q]).size >= 2 for q in range(Q))
+    assert set(np.unique(hm * 2 + vm).tolist()) == {0, 1, 2, 3}
+    sm = rng.integers(0, 2, (F, Q)).astype(np.uint8)
+    tmp = rng.integers(-1, 100, (F, Q)).astype(np.int32)
+    o = oracle.smooth(tile, pal, hm, vm, sm, palpix, pals, 0.08, tmpidx=tmp)
+    assert lib.tiler_debug_psyv_lane_items(1) == 0
+    try:
+        g = smooth_keyframe(tile, pal, hm, vm, sm, palpix, pals, 0.08, tmpidx=tmp)
+    finally:
+        lib.tiler_debug_psyv_lane_items(0)
+    for a, b in zip(g, o):
+        assert np.array_equal(a, b)
+    assert g[4].sum() > 0 and int(np.count_nonzero(g[0] != tile)) > 0  # both merge branches ran
 
 
 def test_smooth_single_frame_is_identity(gpu):

@@ -148,6 +148,7 @@ _SIGS = {
     "tiler_make_tiles_unique_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_int,
                                             c_void_p]),
     "tiler_debug_unique": (c_int, [c_int]),
+    "tiler_debug_psyv_lane_items": (c_int, [ctypes.c_int64]),
     "tiler_lzma_encode": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_uint32, c_int, c_void_p, c_size_t,
                                   c_void_p]),
 }

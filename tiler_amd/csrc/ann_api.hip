@@ -1191,6 +1191,8 @@ int tiler_psyv_batch(int n, const int32_t *rgb, int n_tiles, const uint8_t *palp
                            out32);
 }
 
+int tiler_debug_psyv_lane_items(int64_t min_items) { return psyv_lane_items_debug((long)min_items); }
+
 static int set_maps_one(ann_kdtree *t, const int32_t *tr_tile, const int32_t *tr_pal, const uint8_t *tr_attr) {
     DevScope ds(t->dev);
     NNIndex *ix = t->ix;

@@ -7,6 +7,8 @@
 //   - WaveletGS (main.pas:2805-2840): 3 Haar levels, rows then columns, neighbours via ds_bpermute;
 //   - DCT branch (main.pas:3075-3175): sequential 64-term sums against the host-built gDCTLut.
 // HBM traffic per tile: 256 B in (RGB) or 64 B + 64 B palette, 768 B (fp32) / 1536 B (fp64) out.
+#include <atomic>
+
 #include "psyv.hpp"
 #include "psyv_dev.hpp"
 #include "stage.hpp"
@@ -175,6 +177,16 @@ __global__ __launch_bounds__(64) void psyv_dct_items_kernel(PsyvArgs a) {
 }
 
 static constexpr long PSYV_LANE_ITEMS_MIN = 32768;  // C3 bench keyframe (~20k items): 0.04 ms wave-per-item vs 0.31
+static std::atomic<long> g_psyv_lane_items{PSYV_LANE_ITEMS_MIN};  // tiler_debug_psyv_lane_items
+
+int psyv_lane_items_debug(long min_items) {
+    if (min_items < 0) {
+        set_error("tiler_debug_psyv_lane_items: min_items >= 0");
+        return -1;
+    }
+    g_psyv_lane_items = min_items ? min_items : PSYV_LANE_ITEMS_MIN;
+    return 0;
+}
 
 int launch_psyv(PsyvArgs args, hipStream_t stream) {
     if (args.n <= 0) return 0;
@@ -207,7 +219,7 @@ int launch_psyv(PsyvArgs args, hipStream_t stream) {
         else
             hipLaunchKernelGGL(psyv_rgb_haar_kernel<false>, grid, dim3(64), 0, stream, args);
     } else if ((args.flags & PSYV_FROM_PAL) && !(args.flags & (PSYV_WAVELETS | PSYV_LAB)) && !args.rgb &&
-               (!args.flags_per || args.flags_per_mirrors_only) && args.n >= PSYV_LANE_ITEMS_MIN) {
+               (!args.flags_per || args.flags_per_mirrors_only) && args.n >= g_psyv_lane_items.load()) {
         // many items: one lane each (a wave per item below this count: each lane's 12k-add chain would run alone)
         hipLaunchKernelGGL(psyv_dct_items_kernel, dim3((unsigned)((args.n + 63) / 64)), dim3(64), 0, stream, args);
     } else {

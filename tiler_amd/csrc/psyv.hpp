@@ -31,6 +31,7 @@ struct PsyvArgs {
 };
 
 int launch_psyv(PsyvArgs args, hipStream_t stream);
+int psyv_lane_items_debug(long min_items);  // tiler_debug_psyv_lane_items
 
 // host-buffer form (tiler_psyv_batch): palpix [n_tiles][64] and palettes [n_palettes][16] are read only when the
 // descriptors come from palettes (PSYV_FROM_PAL or flags_per); out64 / out32: either or both

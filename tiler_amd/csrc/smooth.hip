@@ -6,8 +6,9 @@
 //   cmp = sqrt(sum_k (cur_k - prev_k)^2 * (1/192)) summed in index order (CompareEuclideanDCTPtr 659-675);
 //   |cmp| <= Strength -> copy the lower-index item across (4102-4113).
 // A descriptor is a pure function of (tile, palette, H, V), and a keyframe's tilemaps reuse few distinct
-// items, so each distinct item's descriptor is computed ONCE (bit-identical: psyv_kernel, fp64 in source
-// order) into a per-call table, and the chain kernel (8 lanes per position) reads one table row per step
+// items, so each distinct item's descriptor is computed ONCE (bit-identical, fp64 in source order: psyv_kernel,
+// one wave per item, below launch_psyv's item threshold, psyv_dct_items_kernel, one lane per item, from it
+// up) into a per-call table, and the chain kernel (8 lanes per position) reads one table row per step
 // (the previous item's row stays in registers) into the sequential fp64 sum.  Distinct items are found with a GPU hash in three passes
 // (insert keys / number the slots / look items up: no spinning on another lane's write).
 #include <math.h>

@@ -439,6 +439,77 @@ int tiler_finish_quantize_order(int n_palettes, const int32_t *use_count, int32_
  * 0 ok, -1 error (tiler_last_error). */
 int tiler_lzma_encode(const uint8_t *src, size_t n, int lc, int lp, int pb, uint32_t dict_size, int eos,
                       uint8_t *dst, size_t cap, size_t *out_len);
+/* The inverse (host code): one LZMA-alone stream at src[0..n) -> dst[0..cap); any valid lc / lp / pb, the end-marker
+ * and the known-size form.  0: done, *out_len = the decoded bytes, *consumed (optional) = the compressed bytes the
+ * stream took, header included, so concatenated streams can be walked.  TILER_LZMA_GROW: cap is too small -- *out_len
+ * holds the size the header gives (known-size form; nothing was decoded) or the bytes that fitted (end-marker form):
+ * grow the buffer and call again.  -1: corrupt or truncated input (tiler_last_error).  Never reads past n or writes
+ * past cap. */
+#define TILER_LZMA_GROW 1
+int tiler_lzma_decode(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, size_t *out_len, size_t *consumed);
+
+/* ---- GTM playback (the reference player, decoders/htmljs/gtm.player.js) ----------------------------
+ * A .gtm file read back: the optional GTMv header + GTMk records, the LZMA-alone streams, the command tokens
+ * (cmd = word & 63, arg = word >> 6), and a player that reproduces the reference player's framebuffer on the GPU.
+ * Stricter than the JS player: a FrameEnd at a position != width * height, a skip or item past the end of the
+ * tilemap, a tile index >= the tile count, a palette index never loaded, an unknown command, a truncated token and a
+ * tile byte >= the palette size are errors naming the frame and the position.  Not supported (errors too): a second
+ * SetDimensions that changes the size or tile count, and a TileSet after the first frame. */
+#define TILER_GTM_SKIP_BLOCK 0
+#define TILER_GTM_SHORT_TILE_IDX 1
+#define TILER_GTM_LONG_TILE_IDX 2
+#define TILER_GTM_LOAD_PALETTE 3
+#define TILER_GTM_FRAME_END 28
+#define TILER_GTM_TILE_SET 29
+#define TILER_GTM_SET_DIMENSIONS 30
+typedef struct tiler_gtm tiler_gtm;
+typedef struct {
+    int32_t width, height;  /* tilemap size in tiles; a frame is 8 width x 8 height pixels */
+    uint32_t frame_ns;      /* SetDimensions' frame length */
+    int32_t palsize;        /* TileSet's palette size */
+    int64_t frames, keyframes, tiles;
+    int64_t pal_rows;       /* R: palette versions, one per LoadPalette */
+    int32_t has_header;     /* 1 when the file starts with GTMv */
+    uint32_t avg_bytes_per_sec, kf_max_bytes_per_sec; /* the header's byte-rate fields (0 without a header) */
+    int32_t streams;        /* LZMA-alone streams decoded */
+    int64_t next_frame;     /* the frame the next play call starts at */
+} tiler_gtm_info_t;
+/* Parse data[0..n) (copied; host code, needs no GPU).  With a header the streams are split by CompressedSize and
+ * decoded on up to `threads` threads (0: min(16, usable CPUs)), each checked to consume exactly its CompressedSize,
+ * and KFCount / FrameCount / the dimensions are cross-checked against the streams; without one they are decoded one
+ * after the other to the end of the data.  max_raw_bytes (0: 1 GiB) caps what one stream, and the tileset, may expand
+ * to; the dense items may take 16 times that.  NULL on error. */
+tiler_gtm *tiler_gtm_open(const uint8_t *data, size_t n, int threads, size_t max_raw_bytes);
+int tiler_gtm_close(tiler_gtm *h);
+int tiler_gtm_info(tiler_gtm *h, tiler_gtm_info_t *info);
+/* Host getters (host memory only): tiles[T][64]; palettes[R][palsize] RGBA dwords as stored (byte 0 = R); the dense
+ * items of frames [f0, f0 + n): tile[n][Q] (-1 = skipped), attrs[n][Q] (pal << 2 | V << 1 | H), palrow[n][Q] (the
+ * palette version in effect when the item was drawn; -1 where skipped) -- any of the three may be NULL; per frame
+ * kf_end[F] (FrameEnd bit 0), skipped[F], undrawn[F] (positions no frame so far has drawn) -- any may be NULL;
+ * kf_start[KF + 1] (each keyframe's first frame, then F); raw[S] / comp[S] bytes of every stream.  0 / -1. */
+int tiler_gtm_tiles(tiler_gtm *h, uint8_t *tiles);
+int tiler_gtm_palettes(tiler_gtm *h, uint32_t *palettes);
+int tiler_gtm_items(tiler_gtm *h, int64_t f0, int64_t n, int32_t *tile, uint16_t *attrs, int32_t *palrow);
+int tiler_gtm_frame_flags(tiler_gtm *h, uint8_t *kf_end, int32_t *skipped, int32_t *undrawn);
+int tiler_gtm_kf_start(tiler_gtm *h, int32_t *kf_start);
+int tiler_gtm_stream_sizes(tiler_gtm *h, uint64_t *raw, uint64_t *comp);
+/* Play the next n frames into HBM on stream (asynchronous; the only calls of a handle that need the device).  A drawn
+ * item writes its 8x8 tile through the palette contents in effect at that moment (H mirrors x, V mirrors y); a
+ * skipped position keeps its pixels, across keyframes and across a later reload of its palette index; a pixel no
+ * item has drawn yet is opaque black.  A pixel is the stream's palette dword as stored, 0xAABBGGRR (AA = 0xFF in this
+ * writer's streams; never drawn: 0xFF000000) -- mask the top byte to compare with the project's 0x00BBGGRR frames.
+ * layout TILER_GTM_TILES: d_rgb[n][Q][64], the project's tile-major frames (tiler_frame_quality_dev takes them);
+ * TILER_GTM_RASTER: d_rgb[n][8 height][8 width], what a player shows.  d_rgb is 16-byte aligned.  d_undrawn[n]
+ * (optional) = the frame's count of never-drawn positions.  Plays sequentially: the handle keeps each position's last
+ * drawn item between calls (seeking to a keyframe is not offered: it is exact only for streams whose keyframes start
+ * with no skipped item, a property of the writer, not of the format).  Returns the frames produced (fewer than n at
+ * the end of the stream, then 0), or -1. */
+#define TILER_GTM_TILES 0
+#define TILER_GTM_RASTER 1
+int64_t tiler_gtm_play_dev(tiler_gtm *h, int64_t n, int layout, int32_t *d_rgb, int32_t *d_undrawn, void *stream);
+/* The same into host arrays. */
+int64_t tiler_gtm_play(tiler_gtm *h, int64_t n, int layout, int32_t *rgb, int32_t *undrawn);
+int tiler_gtm_rewind(tiler_gtm *h); /* the next play call starts at frame 0 with nothing drawn */
 
 #ifdef __cplusplus
 }

@@ -40,6 +40,14 @@ class SearchStats(ctypes.Structure):
                 ("dup_queries", ctypes.c_int64)]
 
 
+class GtmInfo(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("frame_ns", ctypes.c_uint32),
+                ("palsize", ctypes.c_int32), ("frames", ctypes.c_int64), ("keyframes", ctypes.c_int64),
+                ("tiles", ctypes.c_int64), ("pal_rows", ctypes.c_int64), ("has_header", ctypes.c_int32),
+                ("avg_bytes_per_sec", ctypes.c_uint32), ("kf_max_bytes_per_sec", ctypes.c_uint32),
+                ("streams", ctypes.c_int32), ("next_frame", ctypes.c_int64)]
+
+
 class PrepareInfo(ctypes.Structure):
     _fields_ = [("items", ctypes.c_int64), ("candidates", ctypes.c_int64)]
 
@@ -151,6 +159,19 @@ _SIGS = {
     "tiler_debug_psyv_lane_items": (c_int, [ctypes.c_int64]),
     "tiler_lzma_encode": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_uint32, c_int, c_void_p, c_size_t,
                                   c_void_p]),
+    "tiler_lzma_decode": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, P(c_size_t), P(c_size_t)]),
+    "tiler_gtm_open": (c_void_p, [c_void_p, c_size_t, c_int, c_size_t]),
+    "tiler_gtm_close": (c_int, [c_void_p]),
+    "tiler_gtm_info": (c_int, [c_void_p, P(GtmInfo)]),
+    "tiler_gtm_tiles": (c_int, [c_void_p, c_void_p]),
+    "tiler_gtm_palettes": (c_int, [c_void_p, c_void_p]),
+    "tiler_gtm_items": (c_int, [c_void_p, ctypes.c_int64, ctypes.c_int64, c_void_p, c_void_p, c_void_p]),
+    "tiler_gtm_frame_flags": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tiler_gtm_kf_start": (c_int, [c_void_p, c_void_p]),
+    "tiler_gtm_stream_sizes": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "tiler_gtm_play_dev": (ctypes.c_int64, [c_void_p, ctypes.c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "tiler_gtm_play": (ctypes.c_int64, [c_void_p, ctypes.c_int64, c_int, c_void_p, c_void_p]),
+    "tiler_gtm_rewind": (c_int, [c_void_p]),
 }
 
 _lib = None

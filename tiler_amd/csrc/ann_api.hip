@@ -21,6 +21,7 @@
 #include "../../include/tiler_ann.h"
 #include "dither.hpp"
 #include "palette.hpp"
+#include "play.hpp"
 #include "prepare.hpp"
 #include "kmeans.hpp"
 #include "detmath.hpp"
@@ -1593,5 +1594,127 @@ int tiler_make_tiles_unique_dev(uint8_t *d_palpix, uint8_t *d_active, int64_t *d
 }
 
 int tiler_debug_unique(int hash_bits) { return unique_debug(hash_bits); }
+
+// ---- GTM playback: parsing and the getters are host code (no ensure_init); only the play calls need the device ----
+static Player *gtm_handle(tiler_gtm *h, const char *who) {
+    if (!h) set_error(std::string(who) + ": null handle");
+    return reinterpret_cast<Player *>(h);
+}
+
+tiler_gtm *tiler_gtm_open(const uint8_t *data, size_t n, int threads, size_t max_raw_bytes) {
+    return reinterpret_cast<tiler_gtm *>(player_open(data, n, threads, max_raw_bytes));
+}
+
+int tiler_gtm_close(tiler_gtm *h) {
+    if (!h) return 0;
+    Player *p = reinterpret_cast<Player *>(h);
+    if (player_device(p) >= 0) {
+        DevScope ds(player_device(p));
+        player_close(p);
+    } else {
+        player_close(p);
+    }
+    return 0;
+}
+
+int tiler_gtm_info(tiler_gtm *h, tiler_gtm_info_t *info) {
+    Player *p = gtm_handle(h, "gtm_info");
+    if (!p || !info) return -1;
+    const GtmData &g = player_data(p);
+    info->width = g.width;
+    info->height = g.height;
+    info->frame_ns = g.frame_ns;
+    info->palsize = g.palsize;
+    info->frames = g.frames();
+    info->keyframes = g.keyframes();
+    info->tiles = g.n_tiles;
+    info->pal_rows = g.pal_rows();
+    info->has_header = g.has_header ? 1 : 0;
+    info->avg_bytes_per_sec = g.avg_bytes_per_sec;
+    info->kf_max_bytes_per_sec = g.kf_max_bytes_per_sec;
+    info->streams = (int32_t)g.stream_raw.size();
+    info->next_frame = player_next_frame(p);
+    return 0;
+}
+
+extern "C++" {
+template <class T>
+static void copy_out(T *dst, const std::vector<T> &v, size_t at, size_t n) {
+    if (dst && n) memcpy(dst, v.data() + at, n * sizeof(T));
+}
+}
+
+int tiler_gtm_tiles(tiler_gtm *h, uint8_t *tiles) {
+    Player *p = gtm_handle(h, "gtm_tiles");
+    if (!p) return -1;
+    copy_out(tiles, player_data(p).tiles, 0, player_data(p).tiles.size());
+    return 0;
+}
+
+int tiler_gtm_palettes(tiler_gtm *h, uint32_t *palettes) {
+    Player *p = gtm_handle(h, "gtm_palettes");
+    if (!p) return -1;
+    copy_out(palettes, player_data(p).palettes, 0, player_data(p).palettes.size());
+    return 0;
+}
+
+int tiler_gtm_items(tiler_gtm *h, int64_t f0, int64_t n, int32_t *tile, uint16_t *attrs, int32_t *palrow) {
+    Player *p = gtm_handle(h, "gtm_items");
+    if (!p) return -1;
+    const GtmData &g = player_data(p);
+    if (f0 < 0 || n < 0 || f0 > g.frames() || n > g.frames() - f0) {
+        set_error("gtm_items: frames [f0, f0 + n) outside the stream");
+        return -1;
+    }
+    const size_t at = (size_t)f0 * (size_t)g.Q(), cnt = (size_t)n * (size_t)g.Q();
+    copy_out(tile, g.tile, at, cnt);
+    copy_out(attrs, g.attrs, at, cnt);
+    copy_out(palrow, g.palrow, at, cnt);
+    return 0;
+}
+
+int tiler_gtm_frame_flags(tiler_gtm *h, uint8_t *kf_end, int32_t *skipped, int32_t *undrawn) {
+    Player *p = gtm_handle(h, "gtm_frame_flags");
+    if (!p) return -1;
+    const GtmData &g = player_data(p);
+    copy_out(kf_end, g.kf_end, 0, g.kf_end.size());
+    copy_out(skipped, g.skipped, 0, g.skipped.size());
+    copy_out(undrawn, g.undrawn, 0, g.undrawn.size());
+    return 0;
+}
+
+int tiler_gtm_kf_start(tiler_gtm *h, int32_t *kf_start) {
+    Player *p = gtm_handle(h, "gtm_kf_start");
+    if (!p) return -1;
+    copy_out(kf_start, player_data(p).kf_start, 0, player_data(p).kf_start.size());
+    return 0;
+}
+
+int tiler_gtm_stream_sizes(tiler_gtm *h, uint64_t *raw, uint64_t *comp) {
+    Player *p = gtm_handle(h, "gtm_stream_sizes");
+    if (!p) return -1;
+    copy_out(raw, player_data(p).stream_raw, 0, player_data(p).stream_raw.size());
+    copy_out(comp, player_data(p).stream_comp, 0, player_data(p).stream_comp.size());
+    return 0;
+}
+
+int64_t tiler_gtm_play_dev(tiler_gtm *h, int64_t n, int layout, int32_t *d_rgb, int32_t *d_undrawn, void *stream) {
+    Player *p = gtm_handle(h, "gtm_play");
+    if (!p || !ensure_init()) return -1;
+    DevScope ds(ptr_device(d_rgb));
+    return player_play_dev(p, n, layout, d_rgb, d_undrawn, (hipStream_t)stream);
+}
+
+int64_t tiler_gtm_play(tiler_gtm *h, int64_t n, int layout, int32_t *rgb, int32_t *undrawn) {
+    Player *p = gtm_handle(h, "gtm_play");
+    if (!p || !ensure_init()) return -1;
+    DevScope ds(player_device(p) >= 0 ? player_device(p) : ptr_device(nullptr));
+    return player_play_host(p, n, layout, rgb, undrawn);
+}
+
+int tiler_gtm_rewind(tiler_gtm *h) {
+    Player *p = gtm_handle(h, "gtm_rewind");
+    return p ? player_rewind(p) : -1;
+}
 
 }  // extern "C"

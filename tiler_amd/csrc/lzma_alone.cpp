@@ -17,7 +17,7 @@
 #include <cstring>
 #include <vector>
 
-#include "tiler_common.hpp"
+#include "host_error.hpp"
 
 namespace {
 

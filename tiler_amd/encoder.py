@@ -267,13 +267,54 @@ class Encoder:
                                  sm["vm"], sm["smoothed"])
         return render_frames(sm["tile"], sm["pal"], sm["hm"], sm["vm"], *tail)
 
-    def quality(self, frames=None, *, width: int, height: int) -> dict:
+    def _stream_frames(self, data):
+        """The held frames as a GTM player shows them: `data` (.gtm bytes, a path or a binary file holding the whole
+        clip) played on the GPU, the rows of `frame_idx` kept -> (rgb [frames][Q][64] int32 0x00BBGGRR, the top byte
+        of the stream's 0xAABBGGRR masked off; undrawn [frames])."""
+        Q = self.tiles_per_frame
+        with gtm.Stream(data) as st:
+            if st.positions != Q or st.frames != self.n_frames:
+                raise ValueError(f"the stream holds {st.frames} frames of {st.positions} positions, the encoder "
+                                 f"{self.n_frames} of {Q}")
+            rgb = np.zeros((self.frames, Q, 64), np.int32)
+            undrawn = np.zeros(self.frames, np.int32)
+            chunk = max(1, (1 << 27) // (Q * 256))
+            for f0 in range(0, st.frames, chunk):  # a skipped position carries pixels: every frame is played
+                got, und = st.play(chunk, "tiles", chunk)
+                rows = np.nonzero((self.frame_idx >= f0) & (self.frame_idx < f0 + got.shape[0]))[0]
+                rgb[rows] = (got[self.frame_idx[rows] - f0] & 0x00FFFFFF).astype(np.int32)
+                undrawn[rows] = und[self.frame_idx[rows] - f0]
+        return rgb, undrawn
+
+    def verify_stream(self, data=None, *, width: int, height: int, fps: float = 24.0) -> dict:
+        """Closes the loop on SaveStream: plays `data` (default: self.save_stream(width, height, fps)) with the GPU
+        player and compares every held frame, top byte masked, with render() -- the frames quality() scores.  They
+        are equal exactly when the written bytes (SkipBlock runs, Short/Long indices, the mirror xor, per-keyframe
+        palette loads, LZMA) show what the SmoothedTileMaps say.  Returns frames (compared), differing_frames,
+        differing (their global frame indices), first = (frame, position) of the first difference or None, and
+        undrawn (positions of the held frames nothing had drawn, summed)."""
+        if data is None:
+            data = self.save_stream(width, height, fps)
+        played, undrawn = self._stream_frames(data)
+        rgb, _ = self.render()
+        bad = np.nonzero((played != rgb).any(axis=(1, 2)))[0]
+        first = None
+        if bad.size:
+            r = int(bad[0])
+            first = (int(self.frame_idx[r]), int(np.nonzero((played[r] != rgb[r]).any(axis=1))[0][0]))
+        return {"frames": self.frames, "differing_frames": int(bad.size),
+                "differing": [int(f) for f in self.frame_idx[bad]], "first": first, "undrawn": int(undrawn.sum())}
+
+    def quality(self, frames=None, *, width: int, height: int, stream=None) -> dict:
         """The figure Render shows (lblCorrel main.pas:3488) for every held frame: the frames of render() (the
         SmoothedTileMaps if Smooth has run, i.e. the encode as it is written, else the TileMaps) scored against
         `frames` ([held frames][Q][64], default: the source frames given to the constructor).  width / height in
         pixels as for save_stream (the Video carries only Q, and the figure's transposed half depends on the
-        shape).  Returns per-frame corr (bit-identical to ComputeCorrelationBGR), psnr, sse [.][3], and the
-        rendered frames (rgb, invalid).  A DistributedEncoder returns its own frames' values (rows as `frame_idx`)."""
+        shape).  stream: .gtm bytes, a path or a binary file of the whole clip -> the file's frames, played on the
+        GPU, are scored instead of the in-memory tilemaps (`invalid` is then the never-drawn positions per frame).
+        Returns per-frame corr (bit-identical to ComputeCorrelationBGR), psnr, sse [.][3], and the
+        rendered frames (rgb, invalid).  A DistributedEncoder returns its own frames' values (rows as `frame_idx`);
+        neither this nor verify_stream is a collective."""
         from .quality import frame_quality, psnr
         Q = self.tiles_per_frame
         tm_w, tm_h = int(width) // 8, int(height) // 8
@@ -282,7 +323,7 @@ class Encoder:
         src = np.asarray(self.frame_rgb if frames is None else frames)
         if src.size != self.frames * Q * 64:
             raise ValueError("quality: frames must be the held frames, [frames][Q][64]")
-        rgb, invalid = self.render()
+        rgb, invalid = self.render() if stream is None else self._stream_frames(stream)
         corr, sse = frame_quality(src, rgb, tm_w, tm_h)
         return {"corr": corr, "psnr": psnr(sse, tm_w, tm_h), "sse": sse, "rgb": rgb, "invalid": invalid}
 
@@ -364,6 +405,14 @@ class DistributedEncoder(Encoder):
         """btnReindexClick main.pas:1208-1221: the UseCount histogram over every rank's keyframes."""
         from . import dist as tdist
         return tdist.allreduce(super()._use_count(T), "sum")
+
+    def verify_stream(self, data=None, *, width: int, height: int, fps: float = 24.0) -> dict:
+        """Encoder.verify_stream over this rank's own frames of a complete file.  Not a collective, so the file
+        must be given: save_stream, which would write it, is one."""
+        if data is None:
+            raise ValueError("verify_stream on a DistributedEncoder needs the complete file (save_stream is a "
+                             "collective; pass save_rank's bytes)")
+        return super().verify_stream(data, width=width, height=height, fps=fps)
 
     def save_stream(self, width: int, height: int, fps: float = 24.0) -> bytes | None:
         """SaveStream as a collective: every rank writes and compresses its own keyframes' streams, rank

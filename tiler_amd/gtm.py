@@ -1,4 +1,6 @@
-"""GTM bitstream writer (SaveStream main.pas:4529-4763) over libANN.so's LZMA-alone encoder.
+"""GTM bitstream writer (SaveStream main.pas:4529-4763) over libANN.so's LZMA-alone encoder, and the playback side:
+`lzma_decode`, `Stream` (a .gtm file parsed by libANN.so's reader and played on the GPU, the reference player
+decoders/htmljs/gtm.player.js) and `load_stream`.
 
 `save_stream` follows the reference procedure step by step:
   header        TGTMHeader (main.pas:103-114) + one TGTMKeyFrameInfo per keyframe (116-124), rewritten at
@@ -22,7 +24,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from ._lib import check, load
+from ._lib import GtmInfo, TilerError, check, last_error, load
 
 GT_SKIP_BLOCK, GT_SHORT_TILE_IDX, GT_LONG_TILE_IDX, GT_LOAD_PALETTE = 0, 1, 2, 3
 GT_FRAME_END, GT_TILE_SET, GT_SET_DIMENSIONS = 28, 29, 30
@@ -196,3 +198,179 @@ def save_stream(palpix, thm, tvm, kf_start, palettes, sm_tile, sm_pal, sm_hm, sm
                                  sm_vm[f0:f1], sm_smoothed[f0:f1], width=width, height=height, fps=fps,
                                  palsize=palsize))
     return assemble_stream(compress_streams(raws, threads), kf_start, width, height, fps)
+
+
+# ---- playback -------------------------------------------------------------------------------------------------------
+LZMA_GROW = 1                # TILER_LZMA_GROW
+MAX_RAW_BYTES = 1 << 30      # per-stream output cap (decompression bombs)
+LAYOUTS = {"tiles": 0, "raster": 1}
+
+
+def _vp(a):
+    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def lzma_decode(data: bytes, max_raw_bytes: int = MAX_RAW_BYTES) -> tuple:
+    """One LZMA-alone stream at the start of `data` (any lc / lp / pb; end-marker or known-size form) ->
+    (raw bytes, compressed bytes consumed), so concatenated streams can be walked.  Corrupt or truncated input, or
+    a stream that expands past max_raw_bytes, raises TilerError."""
+    lib = load()
+    src = np.frombuffer(data, np.uint8) if len(data) else np.zeros(1, np.uint8)
+    cap = min(max_raw_bytes, max(1 << 16, 4 * len(data)))
+    n, used = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    while True:
+        out = np.empty(max(cap, 1), np.uint8)
+        rc = lib.tiler_lzma_decode(_vp(src), len(data), _vp(out), cap, ctypes.byref(n), ctypes.byref(used))
+        if rc == 0:
+            return out[:n.value].tobytes(), used.value
+        check(rc, "tiler_lzma_decode")
+        if cap >= max_raw_bytes or n.value > max_raw_bytes:
+            raise TilerError(f"tiler_lzma_decode: the stream expands past max_raw_bytes ({max_raw_bytes})")
+        cap = min(max_raw_bytes, max(n.value, 4 * cap))
+
+
+class Stream:
+    """A .gtm file opened for playback: bytes, a path or a binary file.  Parsing (header, LZMA, command tokens) is
+    host code and needs no GPU; `play` needs the device.  Stricter than the reference JS player: malformed command
+    streams raise TilerError naming the rule, the frame and the position (include/tiler_ann.h)."""
+
+    def __init__(self, source, threads: int = 0, max_raw_bytes: int = MAX_RAW_BYTES):
+        if isinstance(source, str) or hasattr(source, "__fspath__"):
+            with open(source, "rb") as f:
+                source = f.read()
+        elif hasattr(source, "read"):
+            source = source.read()
+        data = bytes(source)
+        self._lib = load()
+        buf = np.frombuffer(data, np.uint8) if data else np.zeros(1, np.uint8)
+        self._h = self._lib.tiler_gtm_open(_vp(buf), len(data), int(threads), int(max_raw_bytes))
+        if not self._h:
+            raise TilerError(f"tiler_gtm_open failed: {last_error()}")
+        info = GtmInfo()
+        check(self._lib.tiler_gtm_info(self._h, ctypes.byref(info)), "tiler_gtm_info")
+        self.width, self.height, self.frame_ns = info.width, info.height, info.frame_ns
+        self.frames, self.keyframes, self.palsize = info.frames, info.keyframes, info.palsize
+        self.n_tiles, self.pal_rows, self.n_streams = info.tiles, info.pal_rows, info.streams
+        self.header = ({"AverageBytesPerSec": info.avg_bytes_per_sec, "KFMaxBytesPerSec": info.kf_max_bytes_per_sec}
+                       if info.has_header else None)
+
+    def close(self):
+        if self._h:
+            self._lib.tiler_gtm_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if not self._h:
+            raise TilerError("the stream is closed")
+        return self._h
+
+    @property
+    def positions(self) -> int:
+        return self.width * self.height
+
+    @property
+    def next_frame(self) -> int:
+        info = GtmInfo()
+        check(self._lib.tiler_gtm_info(self._handle(), ctypes.byref(info)), "tiler_gtm_info")
+        return info.next_frame
+
+    @property
+    def kf_start(self) -> np.ndarray:
+        """[KF + 1]: the first frame of every keyframe, then the frame count."""
+        out = np.zeros(self.keyframes + 1, np.int32)
+        check(self._lib.tiler_gtm_kf_start(self._handle(), _vp(out)), "tiler_gtm_kf_start")
+        return out
+
+    @property
+    def tiles(self) -> np.ndarray:
+        out = np.zeros((self.n_tiles, 64), np.uint8)
+        check(self._lib.tiler_gtm_tiles(self._handle(), _vp(out)), "tiler_gtm_tiles")
+        return out
+
+    @property
+    def palettes(self) -> np.ndarray:
+        """[R][palsize] uint32 RGBA dwords as stored (0xAABBGGRR): one row per LoadPalette, in stream order."""
+        out = np.zeros((self.pal_rows, self.palsize), np.uint32)
+        check(self._lib.tiler_gtm_palettes(self._handle(), _vp(out)), "tiler_gtm_palettes")
+        return out
+
+    def frame_flags(self) -> tuple:
+        """(kf_end [F] uint8, skipped [F] int32, undrawn [F] int32)."""
+        e, s, u = np.zeros(self.frames, np.uint8), np.zeros(self.frames, np.int32), np.zeros(self.frames, np.int32)
+        check(self._lib.tiler_gtm_frame_flags(self._handle(), _vp(e), _vp(s), _vp(u)), "tiler_gtm_frame_flags")
+        return e, s, u
+
+    def stream_sizes(self) -> tuple:
+        """(raw [S], compressed [S]) bytes of every LZMA stream."""
+        r, c = np.zeros(self.n_streams, np.uint64), np.zeros(self.n_streams, np.uint64)
+        check(self._lib.tiler_gtm_stream_sizes(self._handle(), _vp(r), _vp(c)), "tiler_gtm_stream_sizes")
+        return r, c
+
+    def items(self, f0: int = 0, f1: int | None = None) -> tuple:
+        """The dense items of frames [f0, f1): (tile [n][Q] int32, -1 = skipped; attrs [n][Q] uint16 = pal << 2 |
+        V << 1 | H; palrow [n][Q] int32 = the row of `palettes` in effect when the item was drawn)."""
+        f1 = self.frames if f1 is None else f1
+        n, Q = f1 - f0, self.positions
+        if n < 0:
+            raise ValueError("items: f1 < f0")
+        t, a, r = np.zeros((n, Q), np.int32), np.zeros((n, Q), np.uint16), np.zeros((n, Q), np.int32)
+        check(self._lib.tiler_gtm_items(self._handle(), f0, n, _vp(t), _vp(a), _vp(r)), "tiler_gtm_items")
+        return t, a, r
+
+    def play(self, n: int | None = None, layout: str = "tiles", chunk: int | None = None) -> tuple:
+        """The next n frames (default: to the end) as the reference player shows them, drawn on the GPU `chunk`
+        frames per call (default: about 128 MiB of output).  layout "tiles": rgb [n][Q][64], the project's frames;
+        "raster": rgb [n][8 height][8 width].  Pixels are uint32 0xAABBGGRR as stored in the stream (never drawn:
+        0xFF000000); mask the top byte to compare with the project's 0x00BBGGRR frames.  Returns (rgb, undrawn [n]
+        int32: positions nothing has drawn yet); fewer than n frames at the end of the stream."""
+        if layout not in LAYOUTS:
+            raise ValueError("play: layout is 'tiles' or 'raster'")
+        Q = self.positions
+        left = self.frames - self.next_frame
+        n = left if n is None else min(int(n), left)
+        if n < 0:
+            raise ValueError("play: n < 0")
+        chunk = max(1, (1 << 27) // (Q * 256)) if chunk is None else int(chunk)
+        if chunk <= 0:
+            raise ValueError("play: chunk must be positive")
+        rgb = np.zeros((n, Q * 64), np.uint32)
+        undrawn = np.zeros(n, np.int32)
+        done = 0
+        while done < n:
+            m = min(chunk, n - done)
+            got = check(self._lib.tiler_gtm_play(self._handle(), m, LAYOUTS[layout], _vp(rgb[done:]),
+                                                 _vp(undrawn[done:])), "tiler_gtm_play")
+            if got != m:
+                raise TilerError(f"tiler_gtm_play produced {got} of {m} frames")
+            done += m
+        shape = (n, Q, 64) if layout == "tiles" else (n, self.height * 8, self.width * 8)
+        return rgb.reshape(shape), undrawn
+
+    def play_dev(self, n: int, d_rgb: int, layout: str = "tiles", d_undrawn: int = 0, stream=None) -> int:
+        """The next n frames into HBM (device pointers; d_rgb 16-byte aligned), asynchronous on `stream`; returns
+        the frames produced."""
+        return check(self._lib.tiler_gtm_play_dev(self._handle(), int(n), LAYOUTS[layout],
+                                                  ctypes.c_void_p(int(d_rgb)),
+                                                  ctypes.c_void_p(int(d_undrawn)) if d_undrawn else None,
+                                                  ctypes.c_void_p(int(stream)) if stream else None),
+                     "tiler_gtm_play_dev")
+
+    def rewind(self):
+        check(self._lib.tiler_gtm_rewind(self._handle()), "tiler_gtm_rewind")
+
+
+def load_stream(path) -> Stream:
+    """Open a .gtm file (a path or a binary file) for playback."""
+    return Stream(path)

@@ -409,6 +409,23 @@ int tiler_quantize_palettes(long n_tiles, const int32_t *rgb, const int32_t *pal
 int tiler_quantize_palettes_dev(long n_tiles, const int32_t *d_rgb, const int32_t *d_pal_of, const uint8_t *d_active,
                                 int n_palettes, int palsize, int lookup_bpc, int32_t *palettes, int32_t *use_count,
                                 int32_t *colors, void *stream);
+/* QuantizePalette with the value-at-risk path (chkUseDL3 unticked: DoValueAtRiskBased, main.pas:2256-2394) for
+ * n_pairs (keyframe, palette) pairs at once.  rgb / pal_of / active as above; n_palettes = FPaletteCount (a pair's
+ * PalIdx is pair mod n_palettes; it picks the gPalettePattern row and bounds CmlPct from below by
+ * min(U, palsize * n_palettes)); acc0[n_pairs] = round(FrameCount * FTileMapSize * 64 * PalVAR) of each pair's
+ * keyframe (main.pas:2325-2326: all of the keyframe's tiles, banker's rounding) -> palettes[n_pairs][palsize]
+ * (PaletteIndexes: the picked items sorted by CompareCMULHS on their stored Luma / Val / Sat / Hue),
+ * use_count[n_pairs], stats[n_pairs][4] = U (distinct colours), CmlPct, merges, stop reason (0: Count <= CmlPct,
+ * 1: the round's best difference repeated).  Among colours of equal (Count, Hue, Val, Sat) the list order is colour
+ * value ascending (the reference's unstable QuickSort leaves it undefined).  A pair without a colour (no Active tile)
+ * fails the call, the message names the pair.  acc0 and the outputs are host arrays in both forms.  0 / -1. */
+int tiler_quantize_palettes_var(long n_tiles, const int32_t *rgb, const int32_t *pal_of, const uint8_t *active,
+                                int n_pairs, int palsize, int n_palettes, const int32_t *acc0, int32_t *palettes,
+                                int32_t *use_count, int32_t *stats);
+int tiler_quantize_palettes_var_dev(long n_tiles, const int32_t *d_rgb, const int32_t *d_pal_of,
+                                    const uint8_t *d_active, int n_pairs, int palsize, int n_palettes,
+                                    const int32_t *acc0, int32_t *palettes, int32_t *use_count, int32_t *stats,
+                                    void *stream);
 /* Test hook (process-wide) for the DLv3 merges: at most list_cap listed recount_next entries are kept in LDS
  * (list_cap <= 0 or above the built-in 1024 restores 1024); a smaller cap runs the global-memory overflow and the
  * multi-batch path on small tables.  Results are identical for every cap.  0. */

@@ -125,6 +125,10 @@ _SIGS = {
                                         c_void_p]),
     "tiler_quantize_palettes_dev": (c_int, [c_long, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                             c_void_p, c_void_p, c_void_p]),
+    "tiler_quantize_palettes_var": (c_int, [c_long, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                            c_void_p, c_void_p, c_void_p]),
+    "tiler_quantize_palettes_var_dev": (c_int, [c_long, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                                c_void_p, c_void_p, c_void_p, c_void_p]),
     "tiler_prepare_dither_tiles": (c_int, [c_long, c_void_p, c_int, c_int, c_int, c_int, c_uint32, c_void_p, c_void_p,
                                            c_void_p]),
     "tiler_prepare_dither_tiles_dev": (c_int, [c_long, c_void_p, c_int, c_int, c_int, c_int, c_uint32, c_void_p,

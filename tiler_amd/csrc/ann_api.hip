@@ -1381,6 +1381,24 @@ int tiler_quantize_palettes_dev(long n_tiles, const int32_t *d_rgb, const int32_
                                  use_count, colors, (hipStream_t)stream);
 }
 
+int tiler_quantize_palettes_var(long n_tiles, const int32_t *rgb, const int32_t *pal_of, const uint8_t *active,
+                                int n_pairs, int palsize, int n_palettes, const int32_t *acc0, int32_t *palettes,
+                                int32_t *use_count, int32_t *stats) {
+    if (!ensure_init()) return -1;
+    return quantize_palettes_var_host(n_tiles, rgb, pal_of, active, n_pairs, palsize, n_palettes, acc0, palettes,
+                                      use_count, stats);
+}
+
+int tiler_quantize_palettes_var_dev(long n_tiles, const int32_t *d_rgb, const int32_t *d_pal_of,
+                                    const uint8_t *d_active, int n_pairs, int palsize, int n_palettes,
+                                    const int32_t *acc0, int32_t *palettes, int32_t *use_count, int32_t *stats,
+                                    void *stream) {
+    if (!ensure_init()) return -1;
+    DevScope ds(ptr_device(d_rgb));
+    return quantize_palettes_var_dev(n_tiles, d_rgb, d_pal_of, d_active, n_pairs, palsize, n_palettes, acc0, palettes,
+                                     use_count, stats, (hipStream_t)stream);
+}
+
 int tiler_debug_dl3(int list_cap) {
     dl3_debug(list_cap);
     return 0;

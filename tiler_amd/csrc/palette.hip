@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "palette.hpp"
+#include "palette_cm.hpp"
 #include "stage.hpp"
 
 namespace tiler {
@@ -670,48 +671,6 @@ void dl3_debug(int list_cap) {
 
 namespace {
 
-int muldiv_win(int a, int b, int c) {  // Windows MulDiv (unit windows in main.pas's uses): rounded half away from 0
-    if (c == 0) return -1;
-    if (c < 0) {
-        a = -a;
-        c = -c;
-    }
-    const long long prod = (long long)a * b;
-    const bool add = (a < 0 && b < 0) || (a >= 0 && b >= 0);  // the operands' signs pick the rounding direction
-    const long long r = add ? (prod + c / 2) / c : (prod - c / 2) / c;
-    if (r > 2147483647LL || r < -2147483647LL) return -1;
-    return (int)r;
-}
-
-struct CmItem {  // TCountIndexArray (main.pas:193-196)
-    int index, luma;
-    uint8_t hue, sat, val;
-};
-
-CmItem cm_item(int32_t col) {  // FColorMap / FColorMapLuma (main.pas:4835-4847) + RGBToHSV (main.pas:3496-3543)
-    const int rr = col & 255, gg = (col >> 8) & 255, bb = (col >> 16) & 255;
-    const int mx = std::max(rr, std::max(gg, bb)), mn = std::min(rr, std::min(gg, bb));
-    int hh = 0, ss = 0;
-    if (mx != mn) {
-        const int delta = mx - mn;
-        ss = muldiv_win(delta, 255, mx);
-        if (rr == mx)
-            hh = muldiv_win(42, gg - bb, delta);
-        else if (gg == mx)
-            hh = muldiv_win(42, bb - rr, delta) + 84;
-        else
-            hh = muldiv_win(42, rr - gg, delta) + 168;
-        hh %= 252;
-    }
-    CmItem it;
-    it.index = col;
-    it.luma = (rr * 2126 + gg * 7152 + bb * 722) / 10000;
-    it.hue = (uint8_t)(hh & 255);
-    it.sat = (uint8_t)(ss & 255);
-    it.val = (uint8_t)(mx & 255);
-    return it;
-}
-
 int cmp3(int a, int b) { return a < b ? -1 : a > b ? 1 : 0; }
 
 int compare_cmulhs(const CmItem *a, const CmItem *b) {  // main.pas:2081-2090
@@ -743,6 +702,15 @@ void fpc_tlist_sort(std::vector<const CmItem *> &l, int L, int R) {  // TFPList.
 }
 
 }  // namespace
+
+void sort_cm_items(CmItem *items, int n) {
+    std::vector<const CmItem *> l(n);
+    for (int i = 0; i < n; i++) l[i] = &items[i];
+    if (n > 1) fpc_tlist_sort(l, 0, n - 1);
+    std::vector<CmItem> out(n);
+    for (int i = 0; i < n; i++) out[i] = *l[i];
+    std::copy(out.begin(), out.end(), items);
+}
 
 void sort_palette_cmulhs(int32_t *pal, int n) {
     std::vector<CmItem> items(n);

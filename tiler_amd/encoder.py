@@ -22,11 +22,12 @@ from .synth import Video, video_from_frames
 
 
 def load_and_dither(frames, tm_w: int, tm_h: int, palettes_fn=None, n_palettes: int = 8, gamma: int = -1,
-                    use_wavelets: bool = True) -> Video:
+                    use_wavelets: bool = True, use_dl3: bool = True, pal_var: float = 0.95) -> Video:
     """The Load and Dither steps in front of the chain on the GPU (btnLoadClick main.pas:1099-1146, btnDitherClick
     main.pas:858-914): keyframes from the inter-frame correlations, then the keyframe palettes -- PrepareDitherTiles
     (LAB descriptors + k-means -> DitheringPalIndex, PaletteCentroids), QuantizePalette (DLv3), FinishQuantizePalette
-    (tiler_amd.palette) -- and every tile dithered with its palette (FinishDitherTiles).  palettes_fn(k,
+    (tiler_amd.palette); use_dl3=False takes QuantizePalette's value-at-risk path with PalVAR = pal_var (chkUseDL3
+    unticked, sePalVAR / 100) -- and every tile dithered with its palette (FinishDitherTiles).  palettes_fn(k,
     frames_of_keyframe) -> [P][16], when given, replaces the palette generation (with the stand-in palette choice
     of synth.video_from_frames)."""
     from .dither import dither_tiles
@@ -39,7 +40,8 @@ def load_and_dither(frames, tm_w: int, tm_h: int, palettes_fn=None, n_palettes: 
         pals = np.stack([np.asarray(palettes_fn(k, frames[kf_start[k]:kf_start[k + 1]]), np.int32)
                          for k in range(kf_start.size - 1)])
         return video_from_frames(frames, kf_of, pals, dither_tiles)
-    pals, cents, dith, _ = generate_palettes(frames, kf_start, n_palettes, gamma=gamma, use_wavelets=use_wavelets)
+    pals, cents, dith, _ = generate_palettes(frames, kf_start, n_palettes, gamma=gamma, use_wavelets=use_wavelets,
+                                             use_dl3=use_dl3, pal_var=pal_var)
     return video_from_dither(frames, kf_start, pals, cents, dith, dither_tiles)
 
 

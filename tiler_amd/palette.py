@@ -1,6 +1,7 @@
 """Palette generation of the Dither step on libANN.so: QuantizePalette with the default Dennis
 Lee v3 quantizer for every (keyframe, palette) pair at once (main.pas:2154-2254, 2396-2433; dl3quant,
-dlquant/quantizer.c:437-663), and FinishQuantizePalette (main.pas:2435-2480).
+dlquant/quantizer.c:437-663) or, with chkUseDL3 off, its value-at-risk path (main.pas:2256-2394), and
+FinishQuantizePalette (main.pas:2435-2480).
 
 Palette pairs are stacked over keyframes (pair = kf * P + palette), as the Dither path stacks keyframe palettes.
 """
@@ -11,8 +12,10 @@ import ctypes
 import numpy as np
 
 from ._lib import check, load
+from .gtm import fpc_round
 
 DLV3_BPC = 7  # cbxDLBPC default (main.lfm:502)
+PAL_VAR = 0.95  # sePalVAR default 95 (main.lfm:207-216), / 100 (main.pas:890)
 
 
 def _p(a):
@@ -33,6 +36,35 @@ def quantize_palettes(rgb, pal_of, n_pairs: int, palsize: int = 16, bpc: int = D
     check(load().tiler_quantize_palettes(rgb.shape[0], _p(rgb), _p(pal_of), _p(act), n_pairs, palsize, bpc, _p(pal),
                                          _p(uc), _p(colors)), "tiler_quantize_palettes")
     return pal, uc, colors
+
+
+def quantize_palettes_var(rgb, pal_of, n_pairs: int, n_palettes: int, acc0, palsize: int = 16, active=None):
+    """QuantizePalette with the value-at-risk path (chkUseDL3 off, DoValueAtRiskBased main.pas:2256-2394): rgb
+    [n][64] tiles, pal_of [n] pair index (pair = keyframe * n_palettes + palette), acc0 [n_pairs] =
+    round(FrameCount * FTileMapSize * 64 * PalVAR) of each pair's keyframe -> (palettes [n_pairs][palsize] in
+    CompareCMULHS order, use_count [n_pairs], stats [n_pairs][4] = U, CmlPct, merges, stop reason)."""
+    rgb = np.ascontiguousarray(rgb, np.int32).reshape(-1, 64)
+    pal_of = np.ascontiguousarray(pal_of, np.int32)
+    if pal_of.size != rgb.shape[0]:
+        raise ValueError("quantize_palettes_var: one pair index per tile")
+    acc0 = np.ascontiguousarray(acc0, np.int32)
+    if acc0.size != n_pairs:
+        raise ValueError("quantize_palettes_var: one acc0 per pair")
+    act = None if active is None else np.ascontiguousarray(active, np.uint8)
+    pal = np.zeros((n_pairs, palsize), np.int32)
+    uc = np.zeros(n_pairs, np.int32)
+    stats = np.zeros((n_pairs, 4), np.int32)
+    check(load().tiler_quantize_palettes_var(rgb.shape[0], _p(rgb), _p(pal_of), _p(act), n_pairs, palsize, n_palettes,
+                                             _p(acc0), _p(pal), _p(uc), _p(stats)), "tiler_quantize_palettes_var")
+    return pal, uc, stats
+
+
+def var_acc0(kf_start, tiles_per_frame: int, n_palettes: int, pal_var: float) -> np.ndarray:
+    """acc0 of every (keyframe, palette) pair: round(FrameCount * FTileMapSize * 64 * PalVAR), main.pas:2325-2326
+    (every tile of the keyframe, FPC's banker's rounding)."""
+    frames = np.diff(np.asarray(kf_start, np.int64))
+    acc = [fpc_round(int(f) * tiles_per_frame * 64 * float(pal_var)) for f in frames]
+    return np.repeat(np.asarray(acc, np.int32), n_palettes)
 
 
 def finish_quantize_order(use_count) -> np.ndarray:
@@ -85,9 +117,11 @@ def prepare_dither_tiles(rgb, n_palettes: int, gamma: int = -1, use_wavelets: bo
 
 
 def generate_palettes(frames, kf_start, n_palettes: int, palsize: int = 16, gamma: int = -1,
-                      use_wavelets: bool = True, bpc: int = DLV3_BPC, max_iter: int = 0):
+                      use_wavelets: bool = True, bpc: int = DLV3_BPC, max_iter: int = 0, use_dl3: bool = True,
+                      pal_var: float = PAL_VAR):
     """The palette half of btnDitherClick (main.pas:886-907) over all keyframes: PrepareDitherTiles per keyframe,
-    QuantizePalette for every (keyframe, palette) pair in one GPU pass, FinishQuantizePalette per keyframe.
+    QuantizePalette for every (keyframe, palette) pair in one GPU pass -- DLv3, or with use_dl3=False (chkUseDL3
+    unticked) the value-at-risk path with PalVAR = pal_var -- then FinishQuantizePalette per keyframe.
     frames [F][Q][64] RGB, kf_start [KF+1] -> (palettes [KF][P][palsize], centroids [KF][P][192],
     DitheringPalIndex [F*Q], use counts [KF][P])."""
     frames = np.ascontiguousarray(frames, np.int32)
@@ -102,8 +136,12 @@ def generate_palettes(frames, kf_start, n_palettes: int, palsize: int = 16, gamm
         dith[f0 * Q:f1 * Q] = lab
         cent[k] = c
     kf_of_tile = np.repeat(np.repeat(np.arange(KF), np.diff(kf_start)), Q)
-    pal, uc, _ = quantize_palettes(frames.reshape(-1, 64), (kf_of_tile * P + dith).astype(np.int32), KF * P, palsize,
-                                   bpc)
+    pair_of = (kf_of_tile * P + dith).astype(np.int32)
+    if use_dl3:
+        pal, uc, _ = quantize_palettes(frames.reshape(-1, 64), pair_of, KF * P, palsize, bpc)
+    else:
+        pal, uc, _ = quantize_palettes_var(frames.reshape(-1, 64), pair_of, KF * P, P, var_acc0(kf_start, Q, P, pal_var),
+                                           palsize)
     pal = pal.reshape(KF, P, palsize)
     uc = uc.reshape(KF, P)
     for k in range(KF):

@@ -357,11 +357,11 @@ __device__ __forceinline__ bool kd_leaf_dist(const float *__restrict__ qr, const
 // annkSearch replayed exactly for one query (kd_search.cpp; ANN.dll 0x1800128e0, ANNkd_split::ann_search 0x180012b60,
 // ANNkd_leaf::ann_search 0x180012cf0): depth-first, near child first, far child iff its box distance < the current
 // k-th key (eps = 0), leaf scans with the early break, ANNmin_k insertion (equal keys keep the first found).  One
-// thread; the explicit stack holds pending nodes and pending far checks.  Writes idx[0..k) / err[0..k) (missing:
-// -1 / FLT_MAX) and returns the best index (-1: none).  K >= k.
+// thread; the explicit stack holds pending nodes and pending far checks.  Publishes query q's k results (missing:
+// none) and its tilemap item to out.  K >= k.
 template <int K>
-__device__ int kd_replay_query(const KdOrder &o, const float *__restrict__ rows, const float *__restrict__ qr, int k,
-                               int *__restrict__ idx, float *__restrict__ err) {
+__device__ void kd_replay_query(const KdOrder &o, const float *__restrict__ rows, const float *__restrict__ qr, int k,
+                                const ResultSink &out, long q) {
     float mk[K + 1];
     int mi[K + 1];
     int cnt = 0;
@@ -422,10 +422,9 @@ __device__ int kd_replay_query(const KdOrder &o, const float *__restrict__ rows,
     }
     for (int j = 0; j < k; j++) {
         const bool ok = j < cnt;
-        idx[j] = ok ? mi[j] : -1;
-        err[j] = ok ? mk[j] : FLT_MAX;
+        out.put(q, j, k, ok ? mi[j] : -1, ok ? mk[j] : FLT_MAX);
     }
-    return cnt > 0 ? mi[0] : -1;
+    out.put_map(q, cnt > 0 ? mi[0] : -1);
 }
 
 }  // namespace tiler

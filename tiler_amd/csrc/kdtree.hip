@@ -1009,40 +1009,33 @@ int kd_tree_positions(const KdTree *t, int32_t *pos) {
 __global__ __launch_bounds__(256) void kd_verify_kernel(KdOrder o, KdFixArgs a) {
     const long q = (long)blockIdx.x * 256 + threadIdx.x;
     if (q >= a.nq) return;
-    if (a.done && a.done[q]) return;
+    if (a.kd.done && a.kd.done[q]) return;
     const float *qr = a.q + q * o.dd;
-    const float Dk = a.err[q * a.k + a.k - 1];
-    const int i0 = a.idx[q * a.k];
+    const float Dk = a.out.err[q * a.k + a.k - 1];
+    const int i0 = a.out.idx[q * a.k];
     if (i0 < 0 || !(Dk < FLT_MAX)) return;  // empty dataset or fewer than k points: nothing to vouch for
-    const float rb = a.rootbox[q];
+    const float rb = a.kd.rootbox[q];
     bool ok = true;
     for (int j = 0; j < a.k && ok; j++) {
-        const int c = a.idx[q * a.k + j];
+        const int c = a.out.idx[q * a.k + j];
         if ((unsigned)c >= (unsigned)o.n) {
             ok = false;
             break;
         }
         const float fb = kd_path_far_box(o, qr, o.pos[c], rb);
-        const float dc = a.err[q * a.k + j];
+        const float dc = a.out.err[q * a.k + j];
         ok = fb < Dk || (fb <= Dk && dc == Dk);
     }
-    if (!ok || a.force_replay) a.list[atomicAdd(a.count, 1)] = (int)q;
+    if (!ok || a.force_replay) a.kd.list[atomicAdd(a.kd.count, 1)] = (int)q;
 }
 
 // annkSearch replayed exactly: kd_replay_query (kdorder_dev.hpp), one thread per listed query
 template <int K>
 __global__ __launch_bounds__(64) void kd_replay_kernel(KdOrder o, KdFixArgs a) {
-    const int count = *a.count;
+    const int count = *a.kd.count;
     for (int li = blockIdx.x * 64 + threadIdx.x; li < count; li += gridDim.x * 64) {
-        const long q = a.list[li];
-        const int best = kd_replay_query<K>(o, a.rows, a.q + q * o.dd, a.k, a.idx + q * a.k, a.err + q * a.k);
-        if (a.m_tile) {
-            a.m_tile[q] = best >= 0 ? a.tr_tile[best] : -1;
-            a.m_pal[q] = best >= 0 ? a.tr_pal[best] : -1;
-            const int at = best >= 0 ? a.tr_attr[best] : 0;
-            a.m_hm[q] = (at & 1) != 0;
-            a.m_vm[q] = (at & 2) != 0;
-        }
+        const long q = a.kd.list[li];
+        kd_replay_query<K>(o, a.rows, a.q + q * o.dd, a.k, a.out, q);
     }
 }
 
@@ -1362,26 +1355,6 @@ int kd_root_boxes(const KdTree *t, const float *d_q, int nq, float *rootbox, hip
     KTimer tm("kd_verify", stream);
     hipLaunchKernelGGL(kd_rootbox_kernel, dim3((unsigned)std::min<long>(8192, (nq + 3) / 4)), dim3(256), 0, stream,
                        t->view(), d_q, nq, rootbox, done, count);
-    TILER_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-// the replay alone, for queries some earlier kernel already checked and listed in a.list / *a.count
-int kd_replay_listed(const KdTree *t, const KdFixArgs &a, hipStream_t stream) {
-    if (!t || a.nq <= 0) return 0;
-    if (a.k > 32) {
-        set_error("kd replay: k > 32");
-        return -1;
-    }
-    const KdOrder o = t->view();
-    KTimer tm("kd_replay", stream);
-    const dim3 grid(std::min(64, (a.nq + 63) / 64));  // grid-stride over the device-side count
-    if (a.k <= 1)
-        hipLaunchKernelGGL(kd_replay_kernel<1>, grid, dim3(64), 0, stream, o, a);
-    else if (a.k <= 8)
-        hipLaunchKernelGGL(kd_replay_kernel<8>, grid, dim3(64), 0, stream, o, a);
-    else
-        hipLaunchKernelGGL(kd_replay_kernel<32>, grid, dim3(64), 0, stream, o, a);
     TILER_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -8,6 +8,7 @@
 // at m = s + (e - s) / 2 into LO [s, m) and HI [m, e).  The shape is implicit; split positions m are unique,
 // so internal nodes are indexed by m (1..n-1).  Leaves are buckets of <= bs consecutive positions.
 #pragma once
+#include "result_sink.hpp"
 #include "tiler_common.hpp"
 
 namespace tiler {
@@ -24,6 +25,15 @@ struct KdOrder {
     const float *lo = nullptr, *hi = nullptr;        // [n] cell bounds along cd (ANNkd_split::cd_bnds)
     const float *box_lo = nullptr, *box_hi = nullptr; // [dd] enclosing box of the dataset (annEnclRect)
     int n = 0, bs = 1, dd = 0;
+};
+
+// What a search's kernels need of the tree: the tie order and the state of ANN's pruning check (SearchScratch's).
+struct KdCheck {
+    const KdOrder *ko = nullptr;     // tie order: ANN's kd-tree first-found (device view), nullptr = lowest index
+    const float *rootbox = nullptr;  // [nq] each query's annBoxDistance to the tree's box (kd_root_boxes)
+    uint8_t *done = nullptr;         // [nq] 1: the orbit pair pass already checked this query's winner
+    int *list = nullptr, *count = nullptr;  // [nq], [1]: queries whose winner ANN's pruning might have skipped
+                                            // -> exact replay
 };
 
 struct KdTree {
@@ -48,24 +58,15 @@ int kd_tree_positions(const KdTree *t, int32_t *pos);
 struct KdFixArgs {
     const float *rows, *q;
     int nq, k;
-    int *idx;
-    float *err;
-    const int32_t *tr_tile = nullptr, *tr_pal = nullptr;
-    const uint8_t *tr_attr = nullptr;
-    int32_t *m_tile = nullptr, *m_pal = nullptr;
-    uint8_t *m_hm = nullptr, *m_vm = nullptr;
-    int *list = nullptr, *count = nullptr;  // [nq], [1]: queries sent to the replay (count zeroed by the caller)
-    const float *rootbox = nullptr;         // [nq] annBoxDistance of every query (kd_root_boxes)
-    const uint8_t *done = nullptr;          // [nq] or null: 1 = already checked (the pair pass), skip
-    int force_replay = 0;                   // test hook (tiler_debug_force_replay): vouch for nothing
+    ResultSink out;        // the search's results: read by the check, rewritten by the replay
+    KdCheck kd;            // (count zeroed by the caller; done null: check every query)
+    int force_replay = 0;  // test hook (tiler_debug_force_replay): vouch for nothing
 };
 // rootbox[q] = annBoxDistance(q, box) for nq fp32 rows q[nq][dd] (queries whose descriptor kernel did not fuse it)
 // annBoxDistance of every query to the root box; done[nq] / count (optional) are zeroed by the same launch
 int kd_root_boxes(const KdTree *t, const float *d_q, int nq, float *rootbox, hipStream_t stream,
                   uint8_t *done = nullptr, int *count = nullptr);
 int kd_verify_and_replay(const KdTree *t, const KdFixArgs &a, hipStream_t stream);
-// the exact replay of the queries already listed in a.list / *a.count (the small-batch merge checks them itself)
-int kd_replay_listed(const KdTree *t, const KdFixArgs &a, hipStream_t stream);
 // annkPriSearch (ANN.dll 0x1800121a0, k = 1 as ann_kdtree_pri_search 0x180003ef0 calls it) replayed exactly for nq
 // queries, one thread each: box-distance priority queue (ANNpr_queue, 1-based binary heap of at most n entries),
 // leaf scans as annkSearch's, (1 + eps)^2 termination.  heap: kd_pri_heap_bytes(t, nq) of device scratch.

@@ -778,37 +778,16 @@ struct RescoreArgs {
     int lpq;             // lanes (partial lists) per query and split: 2 (32x32 shortlist) or 4 (16x16)
     double N, H, Ec, max_abs_c;
     int ds_int;
-    int *out_idx;
-    float *out_err;
-    int *fb_list;        // tier 2: overflowed queries (MFMA collect pass), count in fb_count
-    int *fb_count;
-    float *thr;          // [nq] tier-2 threshold T (rounded up to fp32)
-    int *ex_list;        // tier 3: exhaustive scan (bad queries, collect-buffer overflow)
-    int *ex_count;
+    ResultSink out;      // (out.h_idx: the small-batch scan only)
+    TierQueues tq;       // tier 2 = the MFMA collect pass; tier 3 also takes its collect-buffer overflows
     int *ccnt;           // [fb_max] collected candidates per tier-2 query
     int *cbuf;           // [fb_max][cap]
-    int cap, fb_max;
-    const int32_t *tr_tile, *tr_pal;
-    const uint8_t *tr_attr;
-    int32_t *m_tile, *m_pal;
-    uint8_t *m_hm, *m_vm;
-    const KdOrder *ko;   // tie order: ANN's kd-tree first-found (device view) or nullptr = the lowest index
-    int *kd_list, *kd_count;  // (unused by the small-batch scan since round 5: its merge replays in place)
-    int force_replay;         // test hook (tiler_debug_force_replay): the check vouches for nothing
-    int prune;                // small-batch scan with a kd-tree of > bs points: the merge kernel runs ANN's pruning
-                              // check (kd_verify_kernel's test) and replays a query it cannot vouch for itself
-    int *h_idx;               // small-batch scan: host-visible copies of the final results (null: none)
-    float *h_err;
+    int cap;
+    KdCheck kd;          // the kernels here use kd.ko alone (kdtree.hip checks the pruning after them)
+    int force_replay;    // test hook (tiler_debug_force_replay): the check vouches for nothing
+    int prune;           // small-batch scan with a kd-tree of > bs points: the merge kernel runs ANN's pruning
+                         // check (kd_verify_kernel's test) and replays a query it cannot vouch for itself
 };
-
-__device__ __forceinline__ void write_map(const RescoreArgs &a, long q, int best) {
-    if (!a.m_tile) return;
-    a.m_tile[q] = best >= 0 ? a.tr_tile[best] : -1;
-    a.m_pal[q] = best >= 0 ? a.tr_pal[best] : -1;
-    const int at = best >= 0 ? a.tr_attr[best] : 0;
-    a.m_hm[q] = (at & 1) != 0;
-    a.m_vm[q] = (at & 2) != 0;
-}
 
 // any() over this lane's group of W lanes (W divides 64)
 template <int W>
@@ -852,7 +831,7 @@ __global__ __launch_bounds__(256) void nn_rescore_kernel(RescoreArgs a) {
     }
     const QStat st = a.qstat[q];
     if (st.flags & QF_BAD) {  // fp16 overflow / non-finite: no valid MFMA keys -> exhaustive scan
-        if (lane == 0) a.ex_list[atomicAdd(a.ex_count, 1)] = (int)q;
+        if (lane == 0) a.tq.ex_list[atomicAdd(a.tq.ex_count, 1)] = (int)q;
         return;
     }
     bool fallback = false;
@@ -894,7 +873,7 @@ __global__ __launch_bounds__(256) void nn_rescore_kernel(RescoreArgs a) {
     // overflow: a full list whose last kept key is <= T may have dropped a needed candidate.  Exact integer keys
     // with L >= k need no check under index order (a lane keeps its best L by (key, index), consistent with the
     // global order), but under ANN's kd order a lane's dropped equal-key entry can rank first
-    if (!exact || a.L < a.k || a.ko) {
+    if (!exact || a.L < a.k || a.kd.ko) {
         const bool last = lane < E && (lane % a.L) == a.L - 1;
         if (grp_any<W>(last && idx >= 0 && (double)key <= T)) fallback = true;
     }
@@ -909,12 +888,12 @@ __global__ __launch_bounds__(256) void nn_rescore_kernel(RescoreArgs a) {
         if (lane == 0) {
             float tf = (float)T;
             if ((double)tf < T) tf = nextafterf(tf, INFINITY);  // keep T an upper bound in fp32
-            a.thr[q] = tf;
-            const int p = atomicAdd(a.fb_count, 1);
-            if (p < a.fb_max)
-                a.fb_list[p] = (int)q;
+            a.tq.thr[q] = tf;
+            const int p = atomicAdd(a.tq.fb_count, 1);
+            if (p < a.tq.fb_max)
+                a.tq.fb_list[p] = (int)q;
             else
-                a.ex_list[atomicAdd(a.ex_count, 1)] = (int)q;
+                a.tq.ex_list[atomicAdd(a.tq.ex_count, 1)] = (int)q;
         }
         return;
     }
@@ -924,13 +903,11 @@ __global__ __launch_bounds__(256) void nn_rescore_kernel(RescoreArgs a) {
     for (int r = 0; r < a.k; r++) {
         float mv = taken ? INFINITY : dist;
         int mi = taken ? 0x7fffffff : di;
-        kd_argmin<W>(a.ko, qrow, mv, mi);
+        kd_argmin<W>(a.kd.ko, qrow, mv, mi);
         if (!taken && di == mi && mi != 0x7fffffff) taken = true;
         if (lane == 0) {
-            const bool ok = mi != 0x7fffffff;
-            a.out_idx[q * a.k + r] = ok ? mi : -1;
-            a.out_err[q * a.k + r] = ok ? mv : FLT_MAX;
-            if (r == 0) write_map(a, q, ok ? mi : -1);
+            a.out.put(q, r, a.k, mi, mv);
+            if (r == 0) a.out.put_map(q, mi);
         }
     }
 }
@@ -942,14 +919,14 @@ __global__ __launch_bounds__(256) void nn_rescore_kernel(RescoreArgs a) {
 
 __global__ __launch_bounds__(256) void nn_rescore2_kernel(RescoreArgs a, int jbase, int chunk) {
     const int lane = threadIdx.x & 63;
-    const int count = min(*a.fb_count - jbase, chunk);
+    const int count = min(*a.tq.fb_count - jbase, chunk);
     for (long j = (long)blockIdx.x * 4 + (threadIdx.x >> 6); j < count; j += (long)gridDim.x * 4) {
-        const long q = a.fb_list[jbase + j];
+        const long q = a.tq.fb_list[jbase + j];
         int n = 0;
         if (lane == 0) n = atomicExch(a.ccnt + j, 0);  // read and clean for the next chunk
         n = __shfl(n, 0, 64);
         if (n > a.cap) {
-            if (lane == 0) a.ex_list[atomicAdd(a.ex_count, 1)] = (int)q;
+            if (lane == 0) a.tq.ex_list[atomicAdd(a.tq.ex_count, 1)] = (int)q;
             continue;
         }
         float bd[8];
@@ -963,8 +940,8 @@ __global__ __launch_bounds__(256) void nn_rescore2_kernel(RescoreArgs a, int jba
         for (int e = lane; e < n; e += 64) {
             const int idx = a.cbuf[j * a.cap + e];
             const float dist = exact_dist(qrow, a.rows + (long)idx * a.d, a.d);
-            if (!kd_less(a.ko, qrow, dist, idx, bd[7], bi[7])) continue;
-            kd_list_insert<8>(a.ko, qrow, bd, bi, dist, idx);  // (dist, tie order); entries arrive in no order
+            if (!kd_less(a.kd.ko, qrow, dist, idx, bd[7], bi[7])) continue;
+            kd_list_insert<8>(a.kd.ko, qrow, bd, bi, dist, idx);  // (dist, tie order); entries arrive in no order
         }
         int ptr = 0;
         for (int r = 0; r < a.k; r++) {
@@ -978,13 +955,11 @@ __global__ __launch_bounds__(256) void nn_rescore2_kernel(RescoreArgs a, int jba
                 }
             float mv = hv;
             int mi = hi;
-            kd_argmin<64>(a.ko, qrow, mv, mi);
+            kd_argmin<64>(a.kd.ko, qrow, mv, mi);
             if (hi == mi && mi != 0x7fffffff) ptr++;
             if (lane == 0) {
-                const bool ok = mi != 0x7fffffff;
-                a.out_idx[q * a.k + r] = ok ? mi : -1;
-                a.out_err[q * a.k + r] = ok ? mv : FLT_MAX;
-                if (r == 0) write_map(a, q, ok ? mi : -1);
+                a.out.put(q, r, a.k, mi, mv);
+                if (r == 0) a.out.put_map(q, mi);
             }
         }
     }
@@ -999,9 +974,9 @@ __global__ __launch_bounds__(256) void nn_exact_kernel(RescoreArgs a, int list_n
     __shared__ float sd[256 * K];
     __shared__ int si[256 * K];
     const int tid = threadIdx.x;
-    const int count = a.ex_list ? *a.ex_count : list_n;
+    const int count = a.tq.ex_list ? *a.tq.ex_count : list_n;
     for (int qi = blockIdx.x; qi < count; qi += gridDim.x) {
-        const long q = a.ex_list ? a.ex_list[qi] : qi;
+        const long q = a.tq.ex_list ? a.tq.ex_list[qi] : qi;
         __syncthreads();
         for (int i = tid; i < a.d; i += 256) sq[i] = a.q[q * a.d + i];
         __syncthreads();
@@ -1024,11 +999,11 @@ __global__ __launch_bounds__(256) void nn_exact_kernel(RescoreArgs a, int list_n
                 if (dist > lim) break;
             }
             if (i < a.d) continue;
-            if (cnt == K && !kd_less(a.ko, sq, dist, j, bd[K - 1], bi[K - 1])) continue;
-            if (!a.ko)
+            if (cnt == K && !kd_less(a.kd.ko, sq, dist, j, bd[K - 1], bi[K - 1])) continue;
+            if (!a.kd.ko)
                 list_insert<K>(bd, bi, dist, j);  // j ascends: an equal key stays behind, as index order wants
             else
-                kd_list_insert<K>(a.ko, sq, bd, bi, dist, j, cnt < K ? cnt : K - 1);
+                kd_list_insert<K>(a.kd.ko, sq, bd, bi, dist, j, cnt < K ? cnt : K - 1);
             if (cnt < K) cnt++;
         }
 #pragma unroll
@@ -1049,7 +1024,7 @@ __global__ __launch_bounds__(256) void nn_exact_kernel(RescoreArgs a, int list_n
                     if (ptr[t] < K) {
                         const float v = sd[th * K + ptr[t]];
                         const int ii = si[th * K + ptr[t]];
-                        if (kd_less(a.ko, sq, v, ii, lv, li)) {
+                        if (kd_less(a.kd.ko, sq, v, ii, lv, li)) {
                             lv = v;
                             li = ii;
                             lt = t;
@@ -1058,13 +1033,11 @@ __global__ __launch_bounds__(256) void nn_exact_kernel(RescoreArgs a, int list_n
                 }
                 float mv = lv;
                 int mi = li;
-                kd_argmin<64>(a.ko, sq, mv, mi);
+                kd_argmin<64>(a.kd.ko, sq, mv, mi);
                 if (lt >= 0 && li == mi && mi != 0x7fffffff) ptr[lt]++;
                 if (tid == 0) {
-                    const bool ok = mi != 0x7fffffff;
-                    a.out_idx[q * a.k + r] = ok ? mi : -1;
-                    a.out_err[q * a.k + r] = ok ? mv : FLT_MAX;
-                    if (r == 0) write_map(a, q, ok ? mi : -1);
+                    a.out.put(q, r, a.k, mi, mv);
+                    if (r == 0) a.out.put_map(q, mi);
                 }
             }
         }
@@ -1164,8 +1137,8 @@ __global__ __launch_bounds__(256) void nn_scan_small_kernel(RescoreArgs a, int n
         for (int q = 0; q < QN; q++) {
             if (q >= nq) break;
             const float *qr = sq + q * SCAN_D_MAX;
-            if (!kd_less(a.ko, qr, dist[q], (int)j, bd[q][K - 1], bi[q][K - 1])) continue;
-            kd_list_insert<K>(a.ko, qr, bd[q], bi[q], dist[q], (int)j);  // keeps (distance, tie order)
+            if (!kd_less(a.kd.ko, qr, dist[q], (int)j, bd[q][K - 1], bi[q][K - 1])) continue;
+            kd_list_insert<K>(a.kd.ko, qr, bd[q], bi[q], dist[q], (int)j);  // keeps (distance, tie order)
         }
     }
     // per query: the workgroup's K best, K rounds of (distance, tie order) argmin over the threads' sorted lists
@@ -1183,7 +1156,7 @@ __global__ __launch_bounds__(256) void nn_scan_small_kernel(RescoreArgs a, int n
                 }
             float mv = v;
             int mi = vi;
-            kd_argmin<64>(a.ko, qr, mv, mi);
+            kd_argmin<64>(a.kd.ko, qr, mv, mi);
             if (lane == 0) {
                 rd[w][r] = mv;
                 ri[w][r] = mi;
@@ -1202,7 +1175,7 @@ __global__ __launch_bounds__(256) void nn_scan_small_kernel(RescoreArgs a, int n
                 }
                 float mv = v;
                 int mi = vi;
-                kd_argmin<64>(a.ko, qr, mv, mi);
+                kd_argmin<64>(a.kd.ko, qr, mv, mi);
                 if (lane < 4 && vi == mi && mi != 0x7fffffff) hp++;
                 if (lane == 0) {
                     const long o = ((long)(qg + q) * nsplit + blockIdx.x) * K + r;
@@ -1224,18 +1197,6 @@ __global__ __launch_bounds__(256) void nn_scan_small_kernel(RescoreArgs a, int n
 // the query value a scalar operand: 3 VALU per (member, dimension).  Each member's sum runs in dimension order --
 // the reference's sequential distance of its own row (orbit_eq_kernel checked row == S_m base with float equality; a
 // -0 / +0 difference squares to the same term) -- so the lists are the row walk's bit for bit.
-// ANN's order of two different present slots x, y of one group for query q (orbit.hip group_before)
-__device__ __forceinline__ bool group_order_before(const GroupOrder *__restrict__ go, const float *__restrict__ q, int x,
-                                                   int y) {
-    const int lo = min(x, y), hi = max(x, y);
-    const int pi = lo == 0 ? hi - 1 : lo == 1 ? hi + 1 : 5;  // (0,1)(0,2)(0,3)(1,2)(1,3)(2,3)
-    const unsigned code = (go->pairs >> (3 * pi)) & 7u;
-    const int node = code & 3;
-    const bool lo_first = (q[go->cd[node]] - go->cv[node]) < 0.0f;
-    const bool low_slot_first = ((code >> 2) & 1) == (unsigned)lo_first;
-    return (x == lo) == low_slot_first;
-}
-
 template <int K>
 __global__ __launch_bounds__(64) void nn_scan_orbit_kernel(RescoreArgs a, const float *__restrict__ qs,
                                                            const int4 *__restrict__ member,
@@ -1289,7 +1250,7 @@ __global__ __launch_bounds__(64) void nn_scan_orbit_kernel(RescoreArgs a, const 
     // the lane's (up to 4) members sorted by (distance, tie order) with a 4-input network (absent slots: the
     // (inf, 0x7fffffff) sentinel, which kd_less puts after every candidate), then K rounds of argmin over the wave
     // An exact tie between two members of the group is decided by the group's cached separating node
-    // (GroupOrder, orbit.hip group_before: one compare) instead of kd_before's root-to-leaf walk.
+    // (GroupOrder, orbit.hpp group_before: one compare) instead of kd_before's root-to-leaf walk.
     float bd[4] = {dist[0], dist[1], dist[2], dist[3]};
     int bi[4] = {mj.x, mj.y, mj.z, mj.w};
     int sl[4] = {0, 1, 2, 3};  // member slots, carried through the swaps
@@ -1303,9 +1264,9 @@ __global__ __launch_bounds__(64) void nn_scan_orbit_kernel(RescoreArgs a, const 
     auto cx = [&](int u, int w) {
         bool less;
         if (bd[w] != bd[u] || bi[w] == 0x7fffffff || bi[u] == 0x7fffffff || !go)
-            less = kd_less(a.ko, qr, bd[w], bi[w], bd[u], bi[u]);
+            less = kd_less(a.kd.ko, qr, bd[w], bi[w], bd[u], bi[u]);
         else
-            less = group_order_before(go, qr, sl[w], sl[u]);
+            less = group_before(go, qr, sl[w], sl[u]);
         if (less) {
             const float td = bd[u];
             const int ti = bi[u], ts = sl[u];
@@ -1334,7 +1295,7 @@ __global__ __launch_bounds__(64) void nn_scan_orbit_kernel(RescoreArgs a, const 
             }
         float mv = v;
         int mi = vi;
-        kd_argmin<64>(a.ko, qr, mv, mi);
+        kd_argmin<64>(a.kd.ko, qr, mv, mi);
         if (vi == mi && mi != 0x7fffffff) ptr++;  // this lane's winner leaves its list
         if (lane == 0) {
             const long o = ((long)q * nsplit + b) * K + r;
@@ -1392,14 +1353,14 @@ __global__ __launch_bounds__(64) void nn_scan_rows_kernel(RescoreArgs a, const f
                 for (int u = 0; u < 16; u++) cur[u] = nxt[u];
         }
         const int j = (int)(b * 64 + lane);
-        if (j < a.n && kd_less(a.ko, qr, dist, j, best, bi)) {
+        if (j < a.n && kd_less(a.kd.ko, qr, dist, j, best, bi)) {
             best = dist;
             bi = j;
         }
     }
     float mv = best;
     int mi = bi;
-    kd_argmin<64>(a.ko, qr, mv, mi);
+    kd_argmin<64>(a.kd.ko, qr, mv, mi);
     if (lane == 0) {
         pd[(long)q * nsplit + sp] = mv;
         pi[(long)q * nsplit + sp] = mi;
@@ -1452,7 +1413,7 @@ __global__ __launch_bounds__(1024) void nn_scan_merge_kernel(RescoreArgs a, int 
                 }
             float mv = v;
             int mi = vi;
-            kd_argmin<64>(a.ko, qr, mv, mi);
+            kd_argmin<64>(a.kd.ko, qr, mv, mi);
             if (lane == 0) {
                 wd[w] = mv;
                 wi[w] = mi;
@@ -1461,7 +1422,7 @@ __global__ __launch_bounds__(1024) void nn_scan_merge_kernel(RescoreArgs a, int 
             if (w == 0) {
                 float v2 = lane < 16 ? wd[lane] : INFINITY;
                 int i2 = lane < 16 ? wi[lane] : 0x7fffffff;
-                kd_argmin<64>(a.ko, qr, v2, i2);
+                kd_argmin<64>(a.kd.ko, qr, v2, i2);
                 if (lane == 0) {
                     rdw[r] = v2;
                     riw[r] = i2;
@@ -1485,13 +1446,8 @@ __global__ __launch_bounds__(1024) void nn_scan_merge_kernel(RescoreArgs a, int 
         if (r == 0) first = ok ? mi : -1;
         Dk = ok ? mv : FLT_MAX;
         if (lane == 0) {
-            a.out_idx[(long)q * a.k + r] = ok ? mi : -1;
-            a.out_err[(long)q * a.k + r] = ok ? mv : FLT_MAX;
-            if (a.h_idx) {
-                a.h_idx[(long)q * a.k + r] = ok ? mi : -1;
-                a.h_err[(long)q * a.k + r] = ok ? mv : FLT_MAX;
-            }
-            if (r == 0) write_map(a, q, ok ? mi : -1);
+            a.out.put(q, r, a.k, mi, mv);
+            if (r == 0) a.out.put_map(q, mi);
         }
     }
     // ANN's pruning along every result's path (kd_verify_kernel's test): vouched for, or replayed exactly here by
@@ -1499,7 +1455,7 @@ __global__ __launch_bounds__(1024) void nn_scan_merge_kernel(RescoreArgs a, int 
     // and replay launches of a coalesced per-tile batch: the wave forms the root box distance from registers, then
     // each half-wave walks one result's path, one level per lane (two results per pass).
     if (a.prune) {
-        const KdOrder o = *a.ko;
+        const KdOrder o = *a.kd.ko;
         if (first >= 0 && Dk < FLT_MAX) {  // uniform
             const float rb = kd_root_box_wave(o, qr, lane);
             bool vouch = true;
@@ -1512,17 +1468,7 @@ __global__ __launch_bounds__(1024) void nn_scan_merge_kernel(RescoreArgs a, int 
                 if (r < a.k) vouch = vouch && valid && (fb < Dk || (fb <= Dk && dr == Dk));
             }
             const bool all = __all(vouch);
-            if ((!all || a.force_replay) && lane == 0) {
-                int *oi = a.out_idx + (long)q * a.k;
-                float *oe = a.out_err + (long)q * a.k;
-                const int best = kd_replay_query<K>(o, a.rows, qr, a.k, oi, oe);
-                write_map(a, q, best);
-                if (a.h_idx)
-                    for (int r = 0; r < a.k; r++) {
-                        a.h_idx[(long)q * a.k + r] = oi[r];
-                        a.h_err[(long)q * a.k + r] = oe[r];
-                    }
-            }
+            if ((!all || a.force_replay) && lane == 0) kd_replay_query<K>(o, a.rows, qr, a.k, a.out, q);
         }
     }
 }
@@ -1868,34 +1814,40 @@ int nn_search_dev(NNIndex *ix, const float *d_q, int nq, int k, int *d_idx, floa
     ra.Ec = ix->maxE;
     ra.ds_int = ix->exact_int ? 1 : 0;
     ra.max_abs_c = ix->max_abs;
-    ra.out_idx = d_idx;
-    ra.out_err = d_err;
-    ra.ko = ix->kd ? ix->kd->d_view : nullptr;
-    ra.h_idx = opt.h_idx;
-    ra.h_err = opt.h_idx ? opt.h_err : nullptr;
+    const bool small = scan_small_takes(ix, nq, k);
+    // the sink, once for every tier: the pinned copies for the small-batch scan alone, the maps for k == 1
+    ResultSink &out = ra.out;
+    out.idx = d_idx;
+    out.err = d_err;
+    if (opt.h_idx && small) {
+        out.h_idx = opt.h_idx;
+        out.h_err = opt.h_err;
+    }
     if (maps && k == 1 && ix->d_tr_tile) {
-        ra.tr_tile = ix->d_tr_tile;
-        ra.tr_pal = ix->d_tr_pal;
-        ra.tr_attr = ix->d_tr_attr;
-        ra.m_tile = maps->tile;
-        ra.m_pal = maps->pal;
-        ra.m_hm = maps->hm;
-        ra.m_vm = maps->vm;
+        out.tr_tile = ix->d_tr_tile;
+        out.tr_pal = ix->d_tr_pal;
+        out.tr_attr = ix->d_tr_attr;
+        out.m_tile = maps->tile;
+        out.m_pal = maps->pal;
+        out.m_hm = maps->hm;
+        out.m_vm = maps->vm;
     }
     ix->last = LastSearch();
     ix->last.queries = ix->last.searched = nq;
     SearchScratch &s = ix->scratch;
     if (!ix->done_event) TILER_HIP_CHECK(hipEventCreateWithFlags(&ix->done_event, hipEventDisableTiming));
-    if (ix->kd && scan_small_takes(ix, nq, k)) {  // the coalesced per-tile batches: scan, merge + pruning check, replay
+    if (ix->kd) {  // ANN's tie order, and its pruning check's state in the scratch
         if (ensure_scratch(ix, nq, 0)) return -1;
+        ra.kd = KdCheck{ix->kd->d_view, s.kd_rootbox, s.kd_done, s.kd_list, s.kd_count};
+    }
+    if (ix->kd && small) {  // the coalesced per-tile batches: scan, merge + pruning check, replay
         ra.prune = ix->kd->n > ix->kd->bs;  // a single bucket: no pruning, position order is exact
         ra.force_replay = g_force_replay.load(std::memory_order_relaxed);
         if (search_core(ix, ra, d_q, nq, k, stream, opt)) return -1;
         TILER_HIP_CHECK(hipEventRecord(ix->done_event, stream));
         return 0;
     }
-    if (ix->kd) {  // ANN's tie order: the pruning check needs every query's box distance and a clean slate
-        if (ensure_scratch(ix, nq, 0)) return -1;
+    if (ix->kd) {  // the pruning check needs every query's box distance and a clean slate
         if (!opt.rootbox_ready) {  // the box distances, with the verify flags and the replay count cleared in the same launch
             if (kd_root_boxes(ix->kd, d_q, nq, s.kd_rootbox, stream, s.kd_done, s.kd_count)) return -1;
         } else {
@@ -1910,19 +1862,7 @@ int nn_search_dev(NNIndex *ix, const float *d_q, int nq, int k, int *d_idx, floa
     }
     // ANN's box pruning along every result's path (queries the pair pass did not already check); the rare query
     // it cannot vouch for is replayed exactly
-    KdFixArgs fa{ix->d_rows, d_q, nq, k, d_idx, d_err};
-    fa.rootbox = s.kd_rootbox;
-    fa.done = s.kd_done;
-    fa.tr_tile = ra.tr_tile;
-    fa.tr_pal = ra.tr_pal;
-    fa.tr_attr = ra.tr_attr;
-    fa.m_tile = ra.m_tile;
-    fa.m_pal = ra.m_pal;
-    fa.m_hm = ra.m_hm;
-    fa.m_vm = ra.m_vm;
-    fa.list = s.kd_list;
-    fa.count = s.kd_count;
-    fa.force_replay = g_force_replay.load(std::memory_order_relaxed);
+    const KdFixArgs fa{ix->d_rows, d_q, nq, k, ra.out, ra.kd, g_force_replay.load(std::memory_order_relaxed)};
     if (kd_verify_and_replay(ix->kd, fa, stream)) return -1;
     TILER_HIP_CHECK(hipEventRecord(ix->done_event, stream));  // what tiler_search_stats reads is final here
     return 0;
@@ -1985,7 +1925,7 @@ static int scan_small(NNIndex *ix, RescoreArgs &ra, int nq, int k, hipStream_t s
     };
     auto scan_o = [&](auto kern) {  // one wave per (64-group block, query), the block count padded to 8 XCDs
         hipLaunchKernelGGL(kern, dim3((unsigned)(((nsplit + 7) / 8) * 8 * nq)), dim3(64), 0, stream, ra, ra.q,
-                           (const int4 *)o->d_member, ra.ko && ix->kd && ix->kd->bs == 1 ? (const GroupOrder *)o->d_gorder : nullptr,
+                           (const int4 *)o->d_member, ra.kd.ko && ix->kd && ix->kd->bs == 1 ? (const GroupOrder *)o->d_gorder : nullptr,
                            (const float4 *)o->d_base, (long)o->G, nsplit, s.key, s.idx);
     };
     // the merge: one split per thread (cross-lane selection only)
@@ -2023,7 +1963,7 @@ static int search_core(NNIndex *ix, RescoreArgs &ra, const float *d_q, int nq, i
     if (!mfma) {
         ix->last.splits = 0;
         ix->last.fallback = nq;
-        ra.ex_list = nullptr;
+        ra.tq.ex_list = nullptr;
         return launch_exact(ra, nq, std::min(nq, 4096), stream);
     }
     // 32x32x16 shortlist: 2 lanes x L = 8 per query (>= 2x the 4-way mirror near-ties of one tile per
@@ -2044,40 +1984,15 @@ static int search_core(NNIndex *ix, RescoreArgs &ra, const float *d_q, int nq, i
     SearchScratch &s = ix->scratch;
     TILER_HIP_CHECK(hipMemsetAsync(s.fb_count, 0, 16, stream));
     ix->last_orbit = 0;
+    // the tier queues, once for both paths (both counts live in fb_count's block); a tier-2 slot for every query
+    // until the generic path sizes its own below
+    ra.tq = TierQueues{s.fb_list, s.fb_count, s.ex_list, s.fb_count + 1, nq, s.thr};
+    ra.qstat = s.qstat;
     if (k == 1 && ix->orbit) {
         // mirror-orbit path (orbit.hip): tier 2 lists every query the rescore cannot settle (fb_max = nq)
-        OrbitTail t{};
-        t.fb_list = s.fb_list;
-        t.fb_count = s.fb_count;
-        t.ex_list = s.ex_list;
-        t.ex_count = s.fb_count + 1;
-        t.fb_max = nq;
-        t.thr = s.thr;
-        t.t2_best = s.t2best;
-        t.flat_cnt = opt.flat_cnt;
-        t.out_idx = ra.out_idx;
-        t.out_err = ra.out_err;
-        t.tr_tile = ra.tr_tile;
-        t.tr_pal = ra.tr_pal;
-        t.tr_attr = ra.tr_attr;
-        t.m_tile = ra.m_tile;
-        t.m_pal = ra.m_pal;
-        t.m_hm = ra.m_hm;
-        t.m_vm = ra.m_vm;
-        t.ko = ra.ko;
-        t.kd_rootbox = s.kd_rootbox;
-        t.kd_done = s.kd_done;
-        t.kd_list = s.kd_list;
-        t.kd_count = s.kd_count;
+        const OrbitTail t{ra.tq, ra.kd, ra.out, s.t2best, opt.flat_cnt, nullptr};
         if (orbit_search(ix, d_q, nq, t, stream, opt.orbit_prepared && k == 1)) return -1;
         ix->last_orbit = 1;
-        ra.qstat = s.qstat;
-        ra.fb_list = s.fb_list;
-        ra.fb_count = s.fb_count;
-        ra.ex_list = s.ex_list;
-        ra.ex_count = s.fb_count + 1;
-        ra.thr = s.thr;
-        ra.fb_max = nq;
         return search_tail(ix, ra, nq, stream, &t);
     }
     // queries -> fragments (same layout and scale as the dataset)
@@ -2105,17 +2020,11 @@ static int search_core(NNIndex *ix, RescoreArgs &ra, const float *d_q, int nq, i
     } else if (dispatch_shortlist<8>(ix, nq, nsplit, bps, stream)) {
         return -1;
     }
-    ra.qstat = s.qstat;
     ra.key = s.key;
     ra.idx = s.idx;
     ra.L = L;
     ra.lpq = lpq;
     ra.nsplit = nsplit;
-    ra.fb_list = s.fb_list;
-    ra.fb_count = s.fb_count;
-    ra.ex_list = s.ex_list;
-    ra.ex_count = s.fb_count + 1;
-    ra.thr = s.thr;
     if (!s.ccnt) TILER_HIP_CHECK(scratch_size_collect(s, true));
     ra.ccnt = s.ccnt;
     ra.cbuf = s.cbuf;
@@ -2123,7 +2032,7 @@ static int search_core(NNIndex *ix, RescoreArgs &ra, const float *d_q, int nq, i
     // tier-2 slots: the collect runs in chunks of TIER2_MAX, as many as the recent tier-2 counts call for (each
     // chunk costs two launches even when empty); an overflowed query beyond the slots goes to the exact tier 3, so
     // the count only shapes the work, never the result
-    ra.fb_max = tier2_slots(ix, nq);
+    ra.tq.fb_max = tier2_slots(ix, nq);
     TILER_HIP_CHECK(hipMemsetAsync(s.ccnt, 0, (size_t)std::min(nq, TIER2_MAX) * sizeof(int), stream));
     {
         KTimer t_rs("nn_rescore", stream);
@@ -2145,7 +2054,7 @@ static int search_tail(NNIndex *ix, const RescoreArgs &ra, int nq, hipStream_t s
     if (orbit) {
         if (orbit_tier2(ix, ra.q, *orbit, nq, stream)) return -1;
     } else {
-        for (int jbase = 0; jbase < ra.fb_max; jbase += TIER2_MAX) {
+        for (int jbase = 0; jbase < ra.tq.fb_max; jbase += TIER2_MAX) {
             if (dispatch_collect(ix, nq, jbase, stream)) return -1;
             KTimer t_r2("nn_rescore2", stream);
             hipLaunchKernelGGL(nn_rescore2_kernel,

@@ -52,6 +52,14 @@ struct SearchScratch {
     size_t cap_q = 0, cap_keys = 0;
 };
 
+// The tier-2 / tier-3 queues of one search (SearchScratch's buffers; the counts stay on the device).
+struct TierQueues {
+    int *fb_list, *fb_count;  // tier 2: the queries the rescore could not settle
+    int *ex_list, *ex_count;  // tier 3: exhaustive scan (bad queries, tier-2 overflow)
+    int fb_max;               // tier-2 slots: a query past them goes to tier 3
+    float *thr;               // [nq] tier-2 threshold T (rounded up to fp32), set by the rescore
+};
+
 // The last search on an index, for tiler_search_stats (reset by every nn_search_dev).
 struct LastSearch {
     long long queries = 0, fallback = 0;

@@ -332,20 +332,6 @@ __global__ __launch_bounds__(256) void orbit_gorder_kernel(KdOrder o, const int 
     out[g] = r;
 }
 
-// ANN's order of two different slots of one group (both present) for query q
-// (go points into HBM: indexing the node there is a plain load, a runtime index into a register copy would
-// put the struct in scratch)
-__device__ __forceinline__ bool group_before(const GroupOrder *__restrict__ go, const float *__restrict__ q, int x,
-                                             int y) {
-    const int lo = min(x, y), hi = max(x, y);
-    const int pi = lo == 0 ? hi - 1 : lo == 1 ? hi + 1 : 5;  // (0,1)(0,2)(0,3)(1,2)(1,3)(2,3)
-    const unsigned code = (go->pairs >> (3 * pi)) & 7u;
-    const int node = code & 3;
-    const bool lo_first = (q[go->cd[node]] - go->cv[node]) < 0.0f;
-    const bool low_slot_first = ((code >> 2) & 1) == (unsigned)lo_first;
-    return (x == lo) == low_slot_first;
-}
-
 // ------------------------------------------------------------------------------------------
 // device: transform + fp16 split (dataset rows: member != null, coefficient cs; queries: qs)
 //   lane l of block b holds row b*32 + (l & 31), k = s*16 + 8*(l >> 5) + j  (A and B maps coincide)
@@ -530,9 +516,8 @@ __global__ __launch_bounds__(NW * 64, 1) void nn_orbit_shortlist_pipe_kernel(con
                                                                          float *__restrict__ out_key,
                                                                          int *__restrict__ out_id, int red_end,
                                                                          const uint8_t *__restrict__ bmask,
-                                                                         int flat_wg0, const uint8_t *__restrict__ bmask0,
-                                                                         const int *__restrict__ flat_cnt,
-                                                                         int flat_base) {
+                                                                         const uint8_t *__restrict__ bmask0,
+                                                                         const int *__restrict__ flat_cnt) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int FRAG_BYTES = CB * OS * 1024;
     constexpr int BUF_BYTES = FRAG_BYTES + CB * 128;
@@ -569,11 +554,10 @@ __global__ __launch_bounds__(NW * 64, 1) void nn_orbit_shortlist_pipe_kernel(con
 
     // blocks [b_begin, r_end): groups with zero isotypic blocks (orbit_build orders them first), block-serial with
     // only the nonzero k-steps; [p_begin, b_end): the pipelined full contraction
-    // workgroups from flat_wg0 on hold flat query tiles only (q' block 0): every candidate block block-serially with
-    // k-steps 0..2, only those streamed
-    // (flat_cnt: the device count of non-flat queries -> first all-flat workgroup; flat_wg0 bounds it)
-    // (flat_base: the launch's first query, when it covers a later part of the batch)
-    if (flat_cnt) flat_wg0 = min(flat_wg0, (max(0, *flat_cnt - flat_base) + NW * QB * 32 - 1) / (NW * QB * 32));
+    // flat_cnt (or null: none) is the device count of the launch's non-flat queries, which come first: the workgroups
+    // past them hold flat query tiles only (q' block 0) and run every candidate block block-serially with k-steps
+    // 0..2, only those streamed
+    const int flat_wg0 = flat_cnt ? (max(0, *flat_cnt) + NW * QB * 32 - 1) / (NW * QB * 32) : 0x7fffffff;
     const bool flat = (int)blockIdx.x >= flat_wg0;
     const int nks = flat ? 3 : OS;
     if (flat) {
@@ -1007,7 +991,7 @@ __device__ __forceinline__ bool orbit_before(const OrbitRescoreArgs &a, const fl
                                              int c2, int gs2) {
     if (a.gorder && gs1 >= 0 && gs2 >= 0 && (gs1 >> 2) == (gs2 >> 2) && c1 != c2)
         return group_before(a.gorder + (gs1 >> 2), q, gs1 & 3, gs2 & 3);
-    return kd_before(a.t.ko, q, c1, c2);
+    return kd_before(a.t.kd.ko, q, c1, c2);
 }
 
 // (dist, ANN order) minimum over a quad / half-wave: each lane holds (distance, candidate, its group code)
@@ -1099,7 +1083,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ORB_RS_WAVE
     }
     if (l == 0) a.pair_cnt[q] = 0;  // the pair pass skips queries settled here or by tiers 2/3
     if (st.flags & 2) {
-        if (l == 0) t.ex_list[atomicAdd(t.ex_count, 1)] = (int)q;
+        if (l == 0) t.tq.ex_list[atomicAdd(t.tq.ex_count, 1)] = (int)q;
         return;
     }
     const int eh = (l / a.L) & 1;
@@ -1120,16 +1104,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ORB_RS_WAVE
         }
     }
     if (__shfl(sel, hbase, 64) < 0) {  // empty dataset
-        if (l == 0) {
-            t.out_idx[q] = -1;
-            t.out_err[q] = FLT_MAX;
-            if (t.m_tile) {
-                t.m_tile[q] = -1;
-                t.m_pal[q] = -1;
-                t.m_hm[q] = 0;
-                t.m_vm[q] = 0;
-            }
-        }
+        if (l == 0) t.out.put1(q, -1, FLT_MAX);
         return;
     }
     const int sl = sel < 0 ? 0 : sel;
@@ -1154,13 +1129,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ORB_RS_WAVE
         if (l == 0) {
             float tf = (float)Tb;
             if ((double)tf < Tb) tf = nextafterf(tf, INFINITY);  // an upper bound in fp32
-            t.thr[q] = tf;
-            const int pidx = atomicAdd(t.fb_count, 1);
-            if (pidx < t.fb_max) {  // always (fb_max = nq)
-                t.fb_list[pidx] = (int)q;
+            t.tq.thr[q] = tf;
+            const int pidx = atomicAdd(t.tq.fb_count, 1);
+            if (pidx < t.tq.fb_max) {  // always (fb_max = nq)
+                t.tq.fb_list[pidx] = (int)q;
                 t.t2_best[pidx] = ~0ull;
             } else {
-                t.ex_list[atomicAdd(t.ex_count, 1)] = (int)q;
+                t.tq.ex_list[atomicAdd(t.tq.ex_count, 1)] = (int)q;
             }
         }
         return;
@@ -1254,16 +1229,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ORB_RS_WAVE
             atomicAdd(t.n_expand, nexp);
             atomicAdd(t.n_expand + 1, nres);
         }
-        const bool ok = bi != 0x7fffffff;
-        t.out_idx[q] = ok ? bi : -1;
-        t.out_err[q] = ok ? bd : FLT_MAX;
-        if (t.m_tile) {
-            t.m_tile[q] = ok ? t.tr_tile[bi] : -1;
-            t.m_pal[q] = ok ? t.tr_pal[bi] : -1;
-            const int at = ok ? t.tr_attr[bi] : 0;
-            t.m_hm[q] = (at & 1) != 0;
-            t.m_vm[q] = (at & 2) != 0;
-        }
+        t.out.put1(q, bi, bd);
     }
 }
 
@@ -1300,24 +1266,14 @@ __global__ __launch_bounds__(256) void nn_orbit_pairs_kernel(OrbitRescoreArgs a)
     }
     const OrbitTail &t = a.t;
     orbit_argmin<ORB_PSLOTS>(a, a.q + q * OD, bd, bi, bg);
-    if (t.ko) {  // ANN's box pruning along the winner's path, with the query row still in cache
-        const bool ok = kd_quad_path_ok(t.ko, a.q + q * OD, t.ko->pos[bi], t.kd_rootbox[q], bd, s);
+    if (t.kd.ko) {  // ANN's box pruning along the winner's path, with the query row still in cache
+        const bool ok = kd_quad_path_ok(t.kd.ko, a.q + q * OD, t.kd.ko->pos[bi], t.kd.rootbox[q], bd, s);
         if (s == 0) {
-            t.kd_done[q] = 1;
-            if (!ok) t.kd_list[atomicAdd(t.kd_count, 1)] = (int)q;
+            t.kd.done[q] = 1;
+            if (!ok) t.kd.list[atomicAdd(t.kd.count, 1)] = (int)q;
         }
     }
-    if (s == 0) {
-        t.out_idx[q] = bi;
-        t.out_err[q] = bd;
-        if (t.m_tile) {
-            t.m_tile[q] = t.tr_tile[bi];
-            t.m_pal[q] = t.tr_pal[bi];
-            const int at = t.tr_attr[bi];
-            t.m_hm[q] = (at & 1) != 0;
-            t.m_vm[q] = (at & 2) != 0;
-        }
-    }
+    if (s == 0) t.out.put1(q, bi, bd);  // (always a candidate: the count is > 0)
 }
 
 // Tier 2 for the queries the orbit rescore could not settle (a lane list was full with its last key <= T_b): every
@@ -1464,24 +1420,16 @@ __global__ __launch_bounds__(256, 2) void nn_orbit_collect_kernel(OrbitCollectAr
 // the tier-2 winners: decode t2_best[j] -> candidate, write the outputs (kd_done stays 0: kd_verify checks them)
 __global__ __launch_bounds__(256) void nn_orbit_t2_final_kernel(OrbitTail t, const float *__restrict__ qrows,
                                                                 const float *__restrict__ rows) {
-    const int count = *t.fb_count;
+    const int count = *t.tq.fb_count;
     for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < count; j += (long)gridDim.x * 256) {
-        const long q = t.fb_list[j];
+        const long q = t.tq.fb_list[j];
         const unsigned long long k = t.t2_best[j];
         if (k == ~0ull) {  // nothing reached T_b: impossible for a finite query (the re-keyed entry does); exhaustive
-            t.ex_list[atomicAdd(t.ex_count, 1)] = (int)q;
+            t.tq.ex_list[atomicAdd(t.tq.ex_count, 1)] = (int)q;
             continue;
         }
-        const int c = kd_unrank(t.ko, qrows + q * OD, (unsigned)k);
-        t.out_idx[q] = c;
-        t.out_err[q] = __uint_as_float((unsigned)(k >> 32));
-        if (t.m_tile) {
-            t.m_tile[q] = t.tr_tile[c];
-            t.m_pal[q] = t.tr_pal[c];
-            const int at = t.tr_attr[c];
-            t.m_hm[q] = (at & 1) != 0;
-            t.m_vm[q] = (at & 2) != 0;
-        }
+        const int c = kd_unrank(t.kd.ko, qrows + q * OD, (unsigned)k);
+        t.out.put1(q, c, __uint_as_float((unsigned)(k >> 32)));
     }
     (void)rows;
 }
@@ -1511,13 +1459,13 @@ int orbit_tier2(NNIndex *ix, const float *d_q, const OrbitTail &tail, int nq, hi
     ca.G = o->G;
     ca.member = o->d_member;
     ca.qfrag = (const half8 *)o->qfrag;
-    ca.fb_list = tail.fb_list;
-    ca.fb_count = tail.fb_count;
-    ca.thr = tail.thr;
+    ca.fb_list = tail.tq.fb_list;
+    ca.fb_count = tail.tq.fb_count;
+    ca.thr = tail.tq.thr;
     ca.blk_per_split = bps;
     ca.rows = ix->d_rows;
     ca.q = d_q;
-    ca.ko = tail.ko;
+    ca.ko = tail.kd.ko;
     ca.best = tail.t2_best;
     {
         KTimer tm("nn_collect", stream);
@@ -2159,7 +2107,7 @@ int orbit_search(NNIndex *ix, const float *d_q, int nq, const OrbitTail &tail, h
                                dim3(ORB_NW * 64), lds, stream, (const half8 *)o->d_frag, o->d_seed, o->gblk,
                                (const half8 *)o->qfrag + (size_t)qb * OS * 64, n, blk, nsplit,
                                o->key + (size_t)qb * 32 * per_q, o->id + (size_t)qb * 32 * per_q, o->red_end,
-                               o->d_bmask, 0x7fffffff, o->d_bmask0, fc, 0);
+                               o->d_bmask, o->d_bmask0, fc);
         };
         if (!mix_full) {
             shortlist(wgs, nsplit, 0, nq, bps, flat_cnt);
@@ -2182,8 +2130,8 @@ int orbit_search(NNIndex *ix, const float *d_q, int nq, const OrbitTail &tail, h
     ra.member = o->d_member;
     ra.dup = o->d_dup;
     ra.rep = o->d_rep;
-    ra.gorder = tail.ko ? o->d_gorder : nullptr;
-    ra.grp_of = tail.ko ? o->d_grp_of : nullptr;
+    ra.gorder = tail.kd.ko ? o->d_gorder : nullptr;
+    ra.grp_of = tail.kd.ko ? o->d_grp_of : nullptr;
     ra.ostat = o->qstat;
     ra.key = o->key;
     ra.id = o->id;

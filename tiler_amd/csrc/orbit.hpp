@@ -69,24 +69,29 @@ struct OrbitIndex {
     long long last_expansions = 0, last_rescored = 0;
 };
 
+// ANN's order of two different slots of one group (both present) for query q
+// (go points into HBM: indexing the node there is a plain load, a runtime index into a register copy would
+// put the struct in scratch)
+__device__ __forceinline__ bool group_before(const GroupOrder *__restrict__ go, const float *__restrict__ q, int x,
+                                             int y) {
+    const int lo = min(x, y), hi = max(x, y);
+    const int pi = lo == 0 ? hi - 1 : lo == 1 ? hi + 1 : 5;  // (0,1)(0,2)(0,3)(1,2)(1,3)(2,3)
+    const unsigned code = (go->pairs >> (3 * pi)) & 7u;
+    const int node = code & 3;
+    const bool lo_first = (q[go->cd[node]] - go->cv[node]) < 0.0f;
+    const bool low_slot_first = ((code >> 2) & 1) == (unsigned)lo_first;
+    return (x == lo) == low_slot_first;
+}
+
 // generic tier-2 / tier-3 plumbing the orbit rescore feeds (owned by nn_search.hip)
 struct OrbitTail {
-    int *fb_list, *fb_count, *ex_list, *ex_count, fb_max;  // fb_max = nq: every tier-2 query has a slot
-    float *thr;                   // [nq] tier-2 threshold T_b (bound-key domain, fp32 rounded up), set by the rescore
+    TierQueues tq;                // fb_max = nq: every tier-2 query has a slot; thr: T_b in the bound-key domain
+    KdCheck kd;                   // (ko != nullptr) the pair pass marks in kd.done the queries whose winner it checked
+    ResultSink out;
     unsigned long long *t2_best;  // [nq] per tier-2 slot: min (distance bits << 32 | kd_rank), ~0 until scored
     const int *flat_cnt;          // device [1] or null: queries >= *flat_cnt are flat tiles (only isotypic block 0 of
                                   // q' is nonzero); read by the shortlist itself, so no host round trip
-    int *out_idx;
-    float *out_err;
-    const int32_t *tr_tile, *tr_pal;
-    const uint8_t *tr_attr;
-    int32_t *m_tile, *m_pal;
-    uint8_t *m_hm, *m_vm;
     int *n_expand;                // optional device counter of block expansions
-    const KdOrder *ko;            // tie order: ANN's kd-tree first-found (device view), nullptr = lowest index
-    const float *kd_rootbox;      // [nq] (ko != nullptr): each query's annBoxDistance to the tree's box
-    uint8_t *kd_done;             // [nq] the pair pass marks the queries whose winner it checked
-    int *kd_list, *kd_count;      // queries whose winner ANN's pruning might have skipped -> exact replay
 };
 
 // 0: orbit index built (ix->orbit), 1: dataset has no exploitable mirror structure, -1: HIP error

@@ -528,6 +528,59 @@ int64_t tiler_gtm_play_dev(tiler_gtm *h, int64_t n, int layout, int32_t *d_rgb, 
 int64_t tiler_gtm_play(tiler_gtm *h, int64_t n, int layout, int32_t *rgb, int32_t *undrawn);
 int tiler_gtm_rewind(tiler_gtm *h); /* the next play call starts at frame 0 with nothing drawn */
 
+/* ---- GTM writing (SaveStream main.pas:4529-4763) -----------------------------------------------------
+ * The SmoothedTileMaps of whole keyframes -> each keyframe's command stream, built on the GPU, LZMA-compressed on
+ * the host (tiler_lzma_encode's lc 8, lp 0, pb 2, dictionary 2^21, end marker), and the .gtm container.
+ * A keyframe's raw stream: for the first keyframe of the file only WriteTiles (SetDimensions, TileSet, 64 B per
+ * tile), then WriteKFAttributes (LoadPalette per palette, colour | 0xFF000000), then per frame, restarted at every
+ * frame: each maximal run of smoothed positions as SkipBlock words of at most 1024 positions, every other position
+ * as Short/LongTileIdx (tile < 65536: one index word, else low then high word) with arg = pal << 2 | (vm ^
+ * tvm[tile]) << 1 | (hm ^ thm[tile]), then FrameEnd (arg 1 on the keyframe's last frame).  Little-endian words.
+ * Checked on the device, before a byte of output is written: a non-smoothed item's tile in [0, tiles) and pal in
+ * [0, min(n_palettes, 256)); the error names the rule and the first offending (frame, position), lowest frame
+ * first.  Smoothed positions are not looked at (the reference never reads their item). */
+typedef struct {
+    const int32_t *tile, *pal;         /* [frames][positions] */
+    const uint8_t *hm, *vm, *smoothed; /* [frames][positions] flags: any non-zero value counts */
+    const uint8_t *palpix;             /* [tiles][64]; read only when first_keyframe is set */
+    const uint8_t *thm, *tvm;          /* [tiles] flags */
+    const int32_t *palettes;           /* [keyframes][n_palettes][palsize] 0x00BBGGRR */
+    const int32_t *kf_start;           /* HOST memory in every form: [keyframes + 1] rows, 0 < ... < frames */
+    int64_t frames, positions, tiles;  /* positions = (width / 8) * (height / 8), at most 2^24 */
+    int32_t keyframes, n_palettes, palsize;
+    int32_t first_keyframe;            /* 1: stream 0 is the file's first keyframe and starts with WriteTiles */
+    int32_t width, height;             /* pixels */
+    double fps;
+} tiler_gtm_source_t;
+/* The raw command streams, back to back in d_raw (HBM, 2-byte aligned): stream k is [raw_off[k], raw_off[k + 1]);
+ * raw_off (host, [keyframes + 1]) is always filled once the input has passed the checks.  d_raw == NULL: only the
+ * sizes; cap < raw_off[keyframes]: -1 with raw_off filled.  The arrays of src are HBM pointers; the call waits once,
+ * for the offsets, then queues the writing kernels on `stream` and returns.  0 / -1. */
+int tiler_gtm_commands_dev(const tiler_gtm_source_t *src, uint8_t *d_raw, size_t cap, int64_t *raw_off, void *stream);
+/* The same from host arrays into a host buffer. */
+int tiler_gtm_commands(const tiler_gtm_source_t *src, uint8_t *raw, size_t cap, int64_t *raw_off);
+/* The compressed streams of the given keyframes, back to back in dst (host), comp_len[keyframes] (host) each one's
+ * size, *out_len their sum: what a caller that holds only some keyframes keeps until every stream is there
+ * (tiler_gtm_assemble).  A stream is copied to the host and handed to a pool of at most `threads` compressor
+ * threads (0: min(16, usable CPUs)) as soon as it is complete.  dst == NULL: only the sizes; cap too small: -1
+ * with *out_len = the size needed.  _dev: src's arrays are HBM pointers and the device work runs on `stream`;
+ * dst, comp_len and out_len are host memory, complete on return. */
+int tiler_gtm_streams_dev(const tiler_gtm_source_t *src, int threads, uint8_t *dst, size_t cap, size_t *comp_len,
+                          size_t *out_len, void *stream);
+int tiler_gtm_streams(const tiler_gtm_source_t *src, int threads, uint8_t *dst, size_t cap, size_t *comp_len,
+                      size_t *out_len);
+/* The .gtm file (host code, needs no GPU) from every keyframe's compressed stream, back to back in comps:
+ * TGTMHeader, one TGTMKeyFrameInfo per keyframe (RawSize 0 as the reference leaves it, KFMaxBytesPerSec over
+ * keyframes k > 0 or the only one, FPC Round = ties to even), the streams.  kf_start[keyframes + 1]: the clip's,
+ * 0 < ... < frame count.  dst / cap / out_len as above. */
+int tiler_gtm_assemble(const uint8_t *comps, const size_t *comp_len, const int32_t *kf_start, int keyframes, int width,
+                       int height, double fps, uint8_t *dst, size_t cap, size_t *out_len);
+/* The whole file: tiler_gtm_streams over every keyframe of the clip (first_keyframe must be 1), then
+ * tiler_gtm_assemble.  dst / cap / out_len as above; on any error dst is left untouched. */
+int tiler_gtm_write_dev(const tiler_gtm_source_t *src, int threads, uint8_t *dst, size_t cap, size_t *out_len,
+                        void *stream);
+int tiler_gtm_write(const tiler_gtm_source_t *src, int threads, uint8_t *dst, size_t cap, size_t *out_len);
+
 #ifdef __cplusplus
 }
 #endif

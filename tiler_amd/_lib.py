@@ -48,6 +48,16 @@ class GtmInfo(ctypes.Structure):
                 ("streams", ctypes.c_int32), ("next_frame", ctypes.c_int64)]
 
 
+class GtmSource(ctypes.Structure):
+    """tiler_gtm_source_t: what SaveStream writes from (host or HBM pointers; kf_start always host)."""
+    _fields_ = [("tile", c_void_p), ("pal", c_void_p), ("hm", c_void_p), ("vm", c_void_p), ("smoothed", c_void_p),
+                ("palpix", c_void_p), ("thm", c_void_p), ("tvm", c_void_p), ("palettes", c_void_p),
+                ("kf_start", c_void_p), ("frames", ctypes.c_int64), ("positions", ctypes.c_int64),
+                ("tiles", ctypes.c_int64), ("keyframes", ctypes.c_int32), ("n_palettes", ctypes.c_int32),
+                ("palsize", ctypes.c_int32), ("first_keyframe", ctypes.c_int32), ("width", ctypes.c_int32),
+                ("height", ctypes.c_int32), ("fps", c_double)]
+
+
 class PrepareInfo(ctypes.Structure):
     _fields_ = [("items", ctypes.c_int64), ("candidates", ctypes.c_int64)]
 
@@ -176,6 +186,14 @@ _SIGS = {
     "tiler_gtm_play_dev": (ctypes.c_int64, [c_void_p, ctypes.c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "tiler_gtm_play": (ctypes.c_int64, [c_void_p, ctypes.c_int64, c_int, c_void_p, c_void_p]),
     "tiler_gtm_rewind": (c_int, [c_void_p]),
+    "tiler_gtm_commands_dev": (c_int, [P(GtmSource), c_void_p, c_size_t, c_void_p, c_void_p]),
+    "tiler_gtm_commands": (c_int, [P(GtmSource), c_void_p, c_size_t, c_void_p]),
+    "tiler_gtm_streams_dev": (c_int, [P(GtmSource), c_int, c_void_p, c_size_t, c_void_p, P(c_size_t), c_void_p]),
+    "tiler_gtm_streams": (c_int, [P(GtmSource), c_int, c_void_p, c_size_t, c_void_p, P(c_size_t)]),
+    "tiler_gtm_assemble": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_size_t,
+                                   P(c_size_t)]),
+    "tiler_gtm_write_dev": (c_int, [P(GtmSource), c_int, c_void_p, c_size_t, P(c_size_t), c_void_p]),
+    "tiler_gtm_write": (c_int, [P(GtmSource), c_int, c_void_p, c_size_t, P(c_size_t)]),
 }
 
 _lib = None

@@ -20,6 +20,7 @@
 
 #include "../../include/tiler_ann.h"
 #include "dither.hpp"
+#include "gtm_write.hpp"
 #include "palette.hpp"
 #include "play.hpp"
 #include "prepare.hpp"
@@ -1733,6 +1734,58 @@ int64_t tiler_gtm_play(tiler_gtm *h, int64_t n, int layout, int32_t *rgb, int32_
 int tiler_gtm_rewind(tiler_gtm *h) {
     Player *p = gtm_handle(h, "gtm_rewind");
     return p ? player_rewind(p) : -1;
+}
+
+// ---- GTM writing: the command words on the device, LZMA and the container on the host (tiler_gtm_assemble: no device)
+int tiler_gtm_commands_dev(const tiler_gtm_source_t *src, uint8_t *d_raw, size_t cap, int64_t *raw_off, void *stream) {
+    if (!ensure_init()) return -1;
+    DevScope ds(ptr_device(src ? src->smoothed : nullptr));
+    return gtm_commands_dev(src, d_raw, cap, raw_off, stream);
+}
+
+int tiler_gtm_commands(const tiler_gtm_source_t *src, uint8_t *raw, size_t cap, int64_t *raw_off) {
+    if (!ensure_init()) return -1;
+    return gtm_commands_host(src, raw, cap, raw_off);
+}
+
+int tiler_gtm_streams_dev(const tiler_gtm_source_t *src, int threads, uint8_t *dst, size_t cap, size_t *comp_len,
+                          size_t *out_len, void *stream) {
+    if (!ensure_init()) return -1;
+    DevScope ds(ptr_device(src ? src->smoothed : nullptr));
+    return gtm_pack_dev(src, threads, false, dst, cap, comp_len, out_len, stream);
+}
+
+int tiler_gtm_streams(const tiler_gtm_source_t *src, int threads, uint8_t *dst, size_t cap, size_t *comp_len,
+                      size_t *out_len) {
+    if (!ensure_init()) return -1;
+    return gtm_pack_host(src, threads, false, dst, cap, comp_len, out_len);
+}
+
+int tiler_gtm_assemble(const uint8_t *comps, const size_t *comp_len, const int32_t *kf_start, int keyframes, int width,
+                       int height, double fps, uint8_t *dst, size_t cap, size_t *out_len) {
+    std::vector<uint8_t> file;
+    if (!gtm_assemble(comps, comp_len, kf_start, keyframes, width, height, fps, file)) return -1;
+    if (out_len) *out_len = file.size();
+    if (!dst) return 0;
+    if (cap < file.size()) {
+        set_error("gtm_assemble: the output buffer holds " + std::to_string(cap) + " bytes, " +
+                  std::to_string(file.size()) + " are needed");
+        return -1;
+    }
+    memcpy(dst, file.data(), file.size());
+    return 0;
+}
+
+int tiler_gtm_write_dev(const tiler_gtm_source_t *src, int threads, uint8_t *dst, size_t cap, size_t *out_len,
+                        void *stream) {
+    if (!ensure_init()) return -1;
+    DevScope ds(ptr_device(src ? src->smoothed : nullptr));
+    return gtm_pack_dev(src, threads, true, dst, cap, nullptr, out_len, stream);
+}
+
+int tiler_gtm_write(const tiler_gtm_source_t *src, int threads, uint8_t *dst, size_t cap, size_t *out_len) {
+    if (!ensure_init()) return -1;
+    return gtm_pack_host(src, threads, true, dst, cap, nullptr, out_len);
 }
 
 }  // extern "C"

@@ -228,12 +228,23 @@ class Encoder:
         self.sm = sm
         return sm
 
-    def _keyframe_streams(self, width: int, height: int, fps: float) -> dict:
+    def _keyframe_streams(self, width: int, height: int, fps: float, gpu: bool = False) -> dict:
         """LZCompress'd command stream of every held keyframe (SaveStream main.pas:4724-4734), compressed
-        concurrently."""
+        concurrently.  gpu: the command words by libANN.so's kernel, LZMA on its thread pool (tiler_gtm_streams)."""
         sm = self.sm
         if sm is None:
             raise RuntimeError("SaveStream needs the SmoothedTileMaps: run do_smooth first")
+        if gpu:
+            if not self.kfs:
+                return {}
+            rows = [self.rows(k) for k in self.kfs]  # the held keyframes' rows follow one another
+            kf_start = np.cumsum([0] + [r.stop - r.start for r in rows])
+            r = slice(rows[0].start, rows[-1].stop)
+            comps = gtm.keyframe_streams_gpu(self.palpix, self.thm, self.tvm, kf_start, self.palettes[self.kfs],
+                                             sm["tile"][r], sm["pal"][r], sm["hm"][r], sm["vm"][r], sm["smoothed"][r],
+                                             width=width, height=height, fps=fps, palsize=self.palsize,
+                                             first_keyframe=self.kfs[0] == 0)
+            return dict(zip(self.kfs, comps))
         raws = []
         for k in self.kfs:
             r = self.rows(k)
@@ -242,9 +253,10 @@ class Encoder:
                                          height=height, fps=fps, palsize=self.palsize))
         return dict(zip(self.kfs, gtm.compress_streams(raws)))
 
-    def save_stream(self, width: int, height: int, fps: float = 24.0) -> bytes:
-        """btnSaveClick -> SaveStream main.pas:4529-4763 (the .gtm bytes; needs do_smooth first)."""
-        comps = self._keyframe_streams(width, height, fps)
+    def save_stream(self, width: int, height: int, fps: float = 24.0, gpu: bool = False) -> bytes:
+        """btnSaveClick -> SaveStream main.pas:4529-4763 (the .gtm bytes; needs do_smooth first).  gpu: the same
+        bytes from the native writer."""
+        comps = self._keyframe_streams(width, height, fps, gpu)
         return gtm.assemble_stream([comps[k] for k in range(self.kf_start.size - 1)], self.kf_start, width, height,
                                    fps)
 
@@ -416,11 +428,11 @@ class DistributedEncoder(Encoder):
                              "collective; pass save_rank's bytes)")
         return super().verify_stream(data, width=width, height=height, fps=fps)
 
-    def save_stream(self, width: int, height: int, fps: float = 24.0) -> bytes | None:
-        """SaveStream as a collective: every rank writes and compresses its own keyframes' streams, rank
-        save_rank receives the others' and assembles the file (None on the other ranks)."""
+    def save_stream(self, width: int, height: int, fps: float = 24.0, gpu: bool = False) -> bytes | None:
+        """SaveStream as a collective: every rank writes and compresses its own keyframes' streams (gpu: with the
+        native writer), rank save_rank receives the others' and assembles the file (None on the other ranks)."""
         from . import dist as tdist
-        comps = tdist.gather_units(self._keyframe_streams(width, height, fps), self.owner_of, self.save_rank)
+        comps = tdist.gather_units(self._keyframe_streams(width, height, fps, gpu), self.owner_of, self.save_rank)
         if comps is None:
             return None
         return gtm.assemble_stream(comps, self.kf_start, width, height, fps)

@@ -12,6 +12,9 @@ decoders/htmljs/gtm.player.js) and `load_stream`.
                   per frame the SmoothedTileMap: runs of Smoothed items -> SkipBlock (count - 1, at most
                   2^10), others -> Short/LongTileIdx with (PalIdx << 2 | VMirror' << 1 | HMirror'), where the
                   mirrors are xored with the tile's canonical flags (4715), then FrameEnd(is last frame of KF).
+`save_stream_gpu` / `keyframe_raw_gpu` / `keyframe_streams_gpu` are the same procedure in libANN.so (tiler_gtm_write,
+tiler_gtm_commands, tiler_gtm_streams): the command words built by a kernel, LZMA and the container in native host
+code.  The Python writer stays as the restatement they are held to, byte for byte.
 The reference takes these bytes verbatim from lzma.exe; this build's encoder makes a different (valid)
 parse, so the compressed bytes differ while everything a decoder returns is identical.
 """
@@ -24,7 +27,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from ._lib import GtmInfo, TilerError, check, last_error, load
+from ._lib import GtmInfo, GtmSource, TilerError, check, last_error, load
 
 GT_SKIP_BLOCK, GT_SHORT_TILE_IDX, GT_LONG_TILE_IDX, GT_LOAD_PALETTE = 0, 1, 2, 3
 GT_FRAME_END, GT_TILE_SET, GT_SET_DIMENSIONS = 28, 29, 30
@@ -198,6 +201,117 @@ def save_stream(palpix, thm, tvm, kf_start, palettes, sm_tile, sm_pal, sm_hm, sm
                                  sm_vm[f0:f1], sm_smoothed[f0:f1], width=width, height=height, fps=fps,
                                  palsize=palsize))
     return assemble_stream(compress_streams(raws, threads), kf_start, width, height, fps)
+
+
+# ---- the native writer (tiler_amd/csrc/gtm_write.hip, gtm_write.cpp) ------------------------------------------------
+def gtm_source(palpix, thm, tvm, kf_start, palettes, tile, pal, hm, vm, smoothed, *, width: int, height: int,
+               fps: float, palsize: int = 16, first_keyframe: bool = True, tiles: int | None = None,
+               n_palettes: int | None = None, frames: int | None = None, positions: int | None = None):
+    """tiler_gtm_source_t over numpy arrays (converted to the ABI's types) or, given as integers, HBM pointers (then
+    tiles, n_palettes, frames and positions must be given).  kf_start [KF + 1]: rows of the arrays, from 0.
+    palettes [KF][P][>= palsize].  Returns (GtmSource, the arrays it points into: keep them alive)."""
+    keep = []
+
+    def ptr(a, dtype, shape=None):
+        if a is None or isinstance(a, int):
+            return a or None
+        a = np.ascontiguousarray(a, dtype)
+        keep.append(a)
+        return a.ctypes.data
+
+    kf = np.ascontiguousarray(kf_start, np.int32)
+    keep.append(kf)
+    if not isinstance(palettes, int):
+        palettes = np.asarray(palettes)[..., :palsize].reshape(kf.size - 1, -1, palsize)
+        n_palettes = palettes.shape[1]
+    if not isinstance(tile, int):
+        tile = np.asarray(tile)
+        frames, positions = tile.shape
+    if not isinstance(thm, int):
+        tiles = np.asarray(thm).size
+    if not isinstance(palpix, int) and palpix is not None:
+        palpix = np.ascontiguousarray(palpix, np.uint8).reshape(-1, 64)
+    as_flag = lambda a: a if isinstance(a, int) else np.asarray(a).astype(np.uint8, copy=False)  # noqa: E731
+    src = GtmSource(ptr(tile, np.int32), ptr(pal, np.int32), ptr(as_flag(hm), np.uint8), ptr(as_flag(vm), np.uint8),
+                    ptr(as_flag(smoothed), np.uint8), ptr(palpix if first_keyframe else None, np.uint8),
+                    ptr(as_flag(thm), np.uint8), ptr(as_flag(tvm), np.uint8), ptr(palettes, np.int32), kf.ctypes.data,
+                    int(frames), int(positions), int(tiles), kf.size - 1, int(n_palettes), int(palsize),
+                    int(bool(first_keyframe)), int(width), int(height), float(fps))
+    return src, keep
+
+
+def _raw_bound(src: GtmSource) -> int:
+    """No raw stream set is longer: the fixed parts + 6 Q + 2 bytes per frame."""
+    return (src.first_keyframe * (24 + 64 * src.tiles) + src.keyframes * src.n_palettes * (4 + 4 * src.palsize) +
+            src.frames * (6 * src.positions + 2))
+
+
+def _sized_call(call, what: str, bound: int):
+    """dst / cap / out_len by tiler_lzma_encode's rules: a buffer of `bound` bytes, grown once if the call asks."""
+    n = ctypes.c_size_t(0)
+    for _ in range(2):
+        out = np.empty(max(bound, 1), np.uint8)
+        if call(out.ctypes.data_as(ctypes.c_void_p), out.size, ctypes.byref(n)) == 0:
+            return out[:n.value]
+        if n.value <= out.size:
+            break
+        bound = n.value
+    raise TilerError(f"{what} failed: {last_error()}")
+
+
+def keyframe_raw_gpu(k: int, palpix, thm, tvm, palettes_k, tile, pal, hm, vm, smoothed, *, width: int, height: int,
+                     fps: float, palsize: int = 16) -> bytes:
+    """keyframe_raw on the GPU (tiler_gtm_commands): the same bytes.  Raises TilerError where keyframe_raw asserts
+    (a tile or palette index out of range at a non-smoothed position)."""
+    F = np.asarray(tile).shape[0]
+    src, keep = gtm_source(palpix, thm, tvm, [0, F], np.asarray(palettes_k)[None], tile, pal, hm, vm, smoothed,
+                           width=width, height=height, fps=fps, palsize=palsize, first_keyframe=k == 0)
+    raw = np.empty(_raw_bound(src), np.uint8)
+    off = np.zeros(2, np.int64)
+    check(load().tiler_gtm_commands(ctypes.byref(src), _vp(raw), raw.size, _vp(off)), "tiler_gtm_commands")
+    return raw[:off[1]].tobytes()
+
+
+def keyframe_streams_gpu(palpix, thm, tvm, kf_start, palettes, sm_tile, sm_pal, sm_hm, sm_vm, sm_smoothed, *,
+                         width: int, height: int, fps: float, palsize: int = 16, first_keyframe: bool = True,
+                         threads: int | None = None) -> list:
+    """The LZCompress'd streams of the given keyframes (tiler_gtm_streams; kf_start: rows of the arrays, from 0;
+    first_keyframe: the first of them is the file's keyframe 0) -- for a caller that holds only some keyframes and
+    assembles the file later (assemble_stream / tiler_gtm_assemble)."""
+    src, keep = gtm_source(palpix, thm, tvm, kf_start, palettes, sm_tile, sm_pal, sm_hm, sm_vm, sm_smoothed,
+                           width=width, height=height, fps=fps, palsize=palsize, first_keyframe=first_keyframe)
+    lens = np.zeros(src.keyframes, np.uint64)
+    raw = _raw_bound(src)
+    lib = load()
+    out = _sized_call(lambda d, cap, n: lib.tiler_gtm_streams(ctypes.byref(src), int(threads or 0), d, cap, _vp(lens), n),
+                      "tiler_gtm_streams", raw + raw // 32 + 4096 * src.keyframes)
+    ends = np.cumsum(lens).astype(np.int64)
+    return [out[e - int(n):e].tobytes() for e, n in zip(ends, lens)]
+
+
+def save_stream_gpu(palpix, thm, tvm, kf_start, palettes, sm_tile, sm_pal, sm_hm, sm_vm, sm_smoothed, width: int,
+                    height: int, fps: float, palsize: int = 16, threads: int | None = None) -> bytes:
+    """save_stream in libANN.so (tiler_gtm_write): the command words on the GPU, LZMA on native threads, the
+    container -- the same file, byte for byte."""
+    src, keep = gtm_source(palpix, thm, tvm, kf_start, palettes, sm_tile, sm_pal, sm_hm, sm_vm, sm_smoothed,
+                           width=width, height=height, fps=fps, palsize=palsize)
+    raw = _raw_bound(src)
+    lib = load()
+    out = _sized_call(lambda d, cap, n: lib.tiler_gtm_write(ctypes.byref(src), int(threads or 0), d, cap, n),
+                      "tiler_gtm_write", raw + raw // 32 + 4096 * src.keyframes + 40 + 28 * src.keyframes)
+    return out.tobytes()
+
+
+def assemble_stream_native(comps, kf_start, width: int, height: int, fps: float) -> bytes:
+    """assemble_stream in libANN.so (tiler_gtm_assemble; host code)."""
+    kf = np.ascontiguousarray(kf_start, np.int32)
+    lens = np.array([len(c) for c in comps], np.uint64)
+    body = np.frombuffer(b"".join(comps), np.uint8) if lens.sum() else np.zeros(1, np.uint8)
+    lib = load()
+    out = _sized_call(lambda d, cap, n: lib.tiler_gtm_assemble(_vp(body), _vp(lens), _vp(kf), kf.size - 1, int(width),
+                                                               int(height), float(fps), d, cap, n),
+                      "tiler_gtm_assemble", int(lens.sum()) + 40 + 28 * max(kf.size - 1, 0))
+    return out.tobytes()
 
 
 # ---- playback -------------------------------------------------------------------------------------------------------

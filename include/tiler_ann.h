@@ -163,7 +163,8 @@ int tiler_set_gamma(double g0, double g1); /* gGamma main.pas:586 / 1441-1447; r
 /* Kernel timing with HIP events on the launching stream (bench/profiling): enable, then read the
  * summed milliseconds and launch count of one kernel family ("psyv", "nn_prep", "nn_shortlist",
  * "nn_rescore", "nn_exact", "smooth", "kmodes", "render", "quality", "reload_match", "unique_insert", "unique_last",
- * "unique_merge", "unique_zero", "ft_dedup": FrameTiling's duplicate-tile passes and scatter).  Reading synchronises the recorded events. */
+ * "unique_merge", "unique_zero", "ft_dedup": FrameTiling's duplicate-tile passes and scatter, "reindex_count",
+ * "reindex_active", "reindex_order", "reindex_gather", "reindex_remap").  Reading synchronises the recorded events. */
 int tiler_timing_enable(int on);
 double tiler_timing_get(const char *kernel, int *launches);
 int tiler_timing_reset(void);
@@ -324,6 +325,55 @@ int tiler_make_tiles_unique_dev(uint8_t *d_palpix, uint8_t *d_active, int64_t *d
 /* Test hook (process-wide): keep only the low hash_bits bits of a tile's hash (0: every tile probes one chain of the
  * table), -1 = the default (all bits).  Results are identical either way; for collision tests only.  0 / -1. */
 int tiler_debug_unique(int hash_bits);
+
+/* ---- Reindex (btnReindexClick main.pas:1199-1230, ReindexTiles main.pas:4483-4527) and the TileMap remap of
+ * FinishMergeTiles (main.pas:3722-3734) ----
+ * Tilemap items are int32, use_count int64, index maps int64 with -1 = none (a merge_index of
+ * tiler_make_tiles_unique is such a map).  Every call: n_items, n, nt in [0, 2^31); 0, or -1 with tiler_last_error();
+ * the result does not depend on the order threads run in (integer atomics only).  The host-array forms stage their
+ * arrays to HBM and run the _dev forms; the _dev forms take device pointers, run on `stream` and wait once (for the
+ * error word, and n_active).
+ *
+ * Use counts (main.pas:1208-1221): use_count[t] = the number of items equal to t, added to what use_count holds when
+ * accumulate != 0 (one call per keyframe's TileMaps, or per rank), after clearing the nt counts when accumulate == 0;
+ * active[t] = (use_count[t] > 0) of the accumulated count (active may be NULL).  An item outside [0, nt) is never
+ * used as an index: the call returns -1, the message names the lowest such item, and use_count / active hold
+ * unspecified values.  n_items = 0 and nt = 0 are allowed. */
+int tiler_tile_use_count(const int32_t *tile, int64_t n_items, int64_t nt, int64_t *use_count, uint8_t *active,
+                         int accumulate);
+int tiler_tile_use_count_dev(const int32_t *d_tile, int64_t n_items, int64_t nt, int64_t *d_use_count,
+                             uint8_t *d_active, int accumulate, void *stream);
+/* The order of ReindexTiles (CompareTileUseCountRev main.pas:4472-4481) over the tiles with active != 0: use_count
+ * descending, old index ascending among equals.  idx_map[nt]: the new index of a tile, -1 for an inactive one;
+ * order[nt]: order[i] = the old index of new tile i for i < *n_active, -1 from there on; *n_active (a host word) =
+ * the active tiles.  An active tile of count 0 is kept and sorts last; an inactive tile is dropped whatever its
+ * count.  Every use_count must lie in [0, 2^31), the reference's Integer: else -1, naming the first such tile. */
+int tiler_reindex_tiles(const uint8_t *active, const int64_t *use_count, int64_t nt, int64_t *idx_map, int64_t *order,
+                        int64_t *n_active);
+int tiler_reindex_tiles_dev(const uint8_t *d_active, const int64_t *d_use_count, int64_t nt, int64_t *d_idx_map,
+                            int64_t *d_order, int64_t *n_active, void *stream);
+/* The tile list in its new order: out[i] = in[order[i]] for i < n, for each pair given (palpix rows of 64 bytes,
+ * thm / tvm bytes, dith_pal, use_count; in arrays [nt], out arrays [n]).  A pair is skipped when both its pointers
+ * are NULL; an output equal to its input is refused (the gather is not in place).  order[i] outside [0, nt) gives -1
+ * (that row is not written).  _dev: palpix and palpix_out 16-byte aligned. */
+int tiler_gather_tiles(const int64_t *order, int64_t n, const uint8_t *palpix, uint8_t *palpix_out, const uint8_t *thm,
+                       uint8_t *thm_out, const uint8_t *tvm, uint8_t *tvm_out, const int32_t *dith_pal,
+                       int32_t *dith_pal_out, const int64_t *use_count, int64_t *use_count_out, int64_t nt);
+int tiler_gather_tiles_dev(const int64_t *d_order, int64_t n, const uint8_t *d_palpix, uint8_t *d_palpix_out,
+                           const uint8_t *d_thm, uint8_t *d_thm_out, const uint8_t *d_tvm, uint8_t *d_tvm_out,
+                           const int32_t *d_dith_pal, int32_t *d_dith_pal_out, const int64_t *d_use_count,
+                           int64_t *d_use_count_out, int64_t nt, void *stream);
+/* TileMap items through an index map, in place: keep_unmapped == 0: tile = map[tile] (ReindexTiles main.pas:4523-4526;
+ * an item of a dropped tile becomes -1); keep_unmapped != 0: tile = map[tile] where that is >= 0, unchanged elsewhere
+ * (FinishMergeTiles).  map[nt], values below 2^31.  An item outside [0, nt) is left as it is and gives -1, naming the
+ * lowest such item; in the _dev form the other items may already be remapped by then (the host-array form leaves the
+ * host array untouched on a failure). */
+int tiler_remap_items(int32_t *tile, int64_t n_items, const int64_t *map, int64_t nt, int keep_unmapped);
+int tiler_remap_items_dev(int32_t *d_tile, int64_t n_items, const int64_t *d_map, int64_t nt, int keep_unmapped,
+                          void *stream);
+/* Test hook (process-wide): the counting strategy of tiler_tile_use_count: 0 = per-workgroup LDS counters in windows
+ * of 65,536 tiles, 1 = wave-combined global atomics, -1 = the default (by nt).  Results are identical.  0 / -1. */
+int tiler_debug_reindex(int strategy);
 
 /* ---- Load-step keyframe detection (btnLoadClick main.pas:1099-1146) ----------------
  * frames[F][tm_h*tm_w][64] int32 0x00BBGGRR (TFrame.Tiles[].RGBPixels, tile-major, as FrameTiling takes

@@ -170,6 +170,17 @@ _SIGS = {
     "tiler_make_tiles_unique_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_int,
                                             c_void_p]),
     "tiler_debug_unique": (c_int, [c_int]),
+    "tiler_tile_use_count": (c_int, [c_void_p, ctypes.c_int64, ctypes.c_int64, c_void_p, c_void_p, c_int]),
+    "tiler_tile_use_count_dev": (c_int, [c_void_p, ctypes.c_int64, ctypes.c_int64, c_void_p, c_void_p, c_int,
+                                         c_void_p]),
+    "tiler_reindex_tiles": (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p, P(ctypes.c_int64)]),
+    "tiler_reindex_tiles_dev": (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p, P(ctypes.c_int64),
+                                        c_void_p]),
+    "tiler_gather_tiles": (c_int, [c_void_p, ctypes.c_int64] + [c_void_p] * 10 + [ctypes.c_int64]),
+    "tiler_gather_tiles_dev": (c_int, [c_void_p, ctypes.c_int64] + [c_void_p] * 10 + [ctypes.c_int64, c_void_p]),
+    "tiler_remap_items": (c_int, [c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int64, c_int]),
+    "tiler_remap_items_dev": (c_int, [c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int64, c_int, c_void_p]),
+    "tiler_debug_reindex": (c_int, [c_int]),
     "tiler_debug_psyv_lane_items": (c_int, [ctypes.c_int64]),
     "tiler_lzma_encode": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_uint32, c_int, c_void_p, c_size_t,
                                   c_void_p]),

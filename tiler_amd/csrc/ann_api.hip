@@ -32,6 +32,7 @@
 #include "orbit.hpp"
 #include "psyv.hpp"
 #include "quality.hpp"
+#include "reindex.hpp"
 #include "reload.hpp"
 #include "smooth.hpp"
 #include "unique.hpp"
@@ -1613,6 +1614,66 @@ int tiler_make_tiles_unique_dev(uint8_t *d_palpix, uint8_t *d_active, int64_t *d
 }
 
 int tiler_debug_unique(int hash_bits) { return unique_debug(hash_bits); }
+
+// ---- Reindex: use counts, the order, the tile-list gather and the tilemap remap (reindex.hip) ----
+int tiler_tile_use_count(const int32_t *tile, int64_t n_items, int64_t nt, int64_t *use_count, uint8_t *active,
+                         int accumulate) {
+    if (!ensure_init()) return -1;
+    return tile_use_count_host(tile, (long)n_items, (long)nt, use_count, active, accumulate);
+}
+
+int tiler_tile_use_count_dev(const int32_t *d_tile, int64_t n_items, int64_t nt, int64_t *d_use_count,
+                             uint8_t *d_active, int accumulate, void *stream) {
+    if (!ensure_init()) return -1;
+    DevScope ds(ptr_device(d_use_count));
+    return tile_use_count_dev(d_tile, (long)n_items, (long)nt, d_use_count, d_active, accumulate, (hipStream_t)stream);
+}
+
+int tiler_reindex_tiles(const uint8_t *active, const int64_t *use_count, int64_t nt, int64_t *idx_map, int64_t *order,
+                        int64_t *n_active) {
+    if (!ensure_init()) return -1;
+    return reindex_tiles_host(active, use_count, (long)nt, idx_map, order, n_active);
+}
+
+int tiler_reindex_tiles_dev(const uint8_t *d_active, const int64_t *d_use_count, int64_t nt, int64_t *d_idx_map,
+                            int64_t *d_order, int64_t *n_active, void *stream) {
+    if (!ensure_init()) return -1;
+    DevScope ds(ptr_device(d_use_count));
+    return reindex_tiles_dev(d_active, d_use_count, (long)nt, d_idx_map, d_order, n_active, (hipStream_t)stream);
+}
+
+int tiler_gather_tiles(const int64_t *order, int64_t n, const uint8_t *palpix, uint8_t *palpix_out, const uint8_t *thm,
+                       uint8_t *thm_out, const uint8_t *tvm, uint8_t *tvm_out, const int32_t *dith_pal,
+                       int32_t *dith_pal_out, const int64_t *use_count, int64_t *use_count_out, int64_t nt) {
+    if (!ensure_init()) return -1;
+    const GatherArgs a{palpix, thm, tvm, dith_pal, use_count, palpix_out, thm_out, tvm_out, dith_pal_out, use_count_out};
+    return gather_tiles_host(order, (long)n, a, (long)nt);
+}
+
+int tiler_gather_tiles_dev(const int64_t *d_order, int64_t n, const uint8_t *d_palpix, uint8_t *d_palpix_out,
+                           const uint8_t *d_thm, uint8_t *d_thm_out, const uint8_t *d_tvm, uint8_t *d_tvm_out,
+                           const int32_t *d_dith_pal, int32_t *d_dith_pal_out, const int64_t *d_use_count,
+                           int64_t *d_use_count_out, int64_t nt, void *stream) {
+    if (!ensure_init()) return -1;
+    DevScope ds(ptr_device(d_order));
+    const GatherArgs a{d_palpix,     d_thm,     d_tvm,     d_dith_pal,     d_use_count,
+                       d_palpix_out, d_thm_out, d_tvm_out, d_dith_pal_out, d_use_count_out};
+    return gather_tiles_dev(d_order, (long)n, a, (long)nt, (hipStream_t)stream);
+}
+
+int tiler_remap_items(int32_t *tile, int64_t n_items, const int64_t *map, int64_t nt, int keep_unmapped) {
+    if (!ensure_init()) return -1;
+    return remap_items_host(tile, (long)n_items, map, (long)nt, keep_unmapped);
+}
+
+int tiler_remap_items_dev(int32_t *d_tile, int64_t n_items, const int64_t *d_map, int64_t nt, int keep_unmapped,
+                          void *stream) {
+    if (!ensure_init()) return -1;
+    DevScope ds(ptr_device(d_tile));
+    return remap_items_dev(d_tile, (long)n_items, d_map, (long)nt, keep_unmapped, (hipStream_t)stream);
+}
+
+int tiler_debug_reindex(int strategy) { return reindex_debug(strategy); }
 
 // ---- GTM playback: parsing and the getters are host code (no ensure_init); only the play calls need the device ----
 static Player *gtm_handle(tiler_gtm *h, const char *who) {

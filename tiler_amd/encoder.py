@@ -8,7 +8,9 @@ MakeUnique -> GlobalTiling -> FrameTiling -> Reindex -> Smooth), as host state +
 Each method is the reference procedure of the same name (file:line in its docstring); the heavy parts
 (K-Modes, the k=8 preselection, candidate descriptors, the FrameTiling search, Smooth) run on the GPU
 through the C ABI, the rest is the reference's host bookkeeping -- MakeTilesUnique too unless the encoder is made
-with gpu_unique=True (tiler_make_tiles_unique; the same result).  SURVEY.md 8(f)-1.
+with gpu_unique=True (tiler_make_tiles_unique; the same result), and Reindex's counts, order and TileMap remaps
+unless it is made with gpu_reindex=True (tiler_tile_use_count, tiler_reindex_tiles, tiler_gather_tiles,
+tiler_remap_items; the same result).  SURVEY.md 8(f)-1.
 """
 from __future__ import annotations
 
@@ -50,10 +52,14 @@ class Encoder:
     None = all).  The tileset (palpix, flags, Active, UseCount) is always the whole clip's.  Tilemap arrays are
     [len(frames)][Q]: row r is frame frames[r]."""
 
-    def __init__(self, v: Video, palsize: int = 16, frames=None, gpu_unique: bool = False):
+    def __init__(self, v: Video, palsize: int = 16, frames=None, gpu_unique: bool = False,
+                 gpu_reindex: bool = False):
         F, Q = v.frames, v.tiles_per_frame
         self.palsize = palsize
         self.gpu_unique = bool(gpu_unique)  # MakeTilesUnique on the GPU (tiler_make_tiles_unique)
+        # UseCount, ReindexTiles and every TileMap remap on the GPU (tiler_tile_use_count, tiler_reindex_tiles,
+        # tiler_gather_tiles, tiler_remap_items); the arrays stay numpy, as with gpu_unique
+        self.gpu_reindex = bool(gpu_reindex)
         self.n_frames = F
         self.kf_start = np.asarray(v.kf_start, np.int64)
         own = np.arange(F) if frames is None else np.asarray(frames, np.int64)
@@ -99,6 +105,9 @@ class Encoder:
     # --- tile-list bookkeeping --------------------------------------------------------------------
     def finish_merge_tiles(self, merge_index):
         """FinishMergeTiles main.pas:3722-3734: TileMap items of merged tiles point at the survivor."""
+        if self.gpu_reindex:
+            self.tile = gt.remap_items_gpu(self.tile, merge_index, keep_unmapped=True)
+            return
         m = np.asarray(merge_index, np.int64)[self.tile]
         self.tile = np.where(m >= 0, m, self.tile)
 
@@ -117,6 +126,15 @@ class Encoder:
     def reindex_tiles(self):
         """ReindexTiles main.pas:4483-4527: drop inactive tiles, order by (UseCount desc, old index asc),
         remap every TileMap."""
+        if self.gpu_reindex:
+            idx_map, order = gt.reindex_tiles_gpu(self.active, self.use_count, return_order=True)
+            self.palpix, self.thm, self.tvm, self.dith_pal, self.use_count = gt.gather_tiles_gpu(
+                order, self.palpix, self.thm, self.tvm, self.dith_pal, self.use_count)
+            self.active = np.ones(order.size, np.uint8)
+            self.tile = gt.remap_items_gpu(self.tile, idx_map)
+            if self.sm is not None:
+                self.sm["tile"] = gt.remap_items_gpu(self.sm["tile"], idx_map)
+            return
         idx_map = gt.reindex_tiles(self.active, self.use_count)
         keep = np.nonzero(idx_map >= 0)[0]
         order = np.empty(keep.size, np.int64)
@@ -206,6 +224,8 @@ class Encoder:
         return errs
 
     def _use_count(self, T: int) -> np.ndarray:
+        if self.gpu_reindex:
+            return gt.use_count_gpu(self.tile, T)[0]
         return np.bincount(self.tile.ravel(), minlength=T).astype(np.int64)
 
     def do_reindex(self):
@@ -371,7 +391,7 @@ class DistributedEncoder(Encoder):
     gets the same answer; sharding the match across ranks is out of scope."""
 
     def __init__(self, v: Video, palsize: int = 16, device: int | None = None, save_rank: int = 0,
-                 gpu_unique: bool = False):
+                 gpu_unique: bool = False, gpu_reindex: bool = False):
         import os
 
         import torch
@@ -391,7 +411,7 @@ class DistributedEncoder(Encoder):
         mine = sorted(self.plan[self.rank])
         own = np.concatenate([np.arange(kf_start[k], kf_start[k + 1]) for k in mine]) if mine \
             else np.zeros(0, np.int64)
-        super().__init__(v, palsize, frames=own, gpu_unique=gpu_unique)
+        super().__init__(v, palsize, frames=own, gpu_unique=gpu_unique, gpu_reindex=gpu_reindex)
         self.device = int(os.environ.get("LOCAL_RANK", "0")) if device is None else int(device)
         if self.device >= 0:  # device = -1: no GPU binding (host-side steps only, e.g. SaveStream in CPU tests)
             check(load().tiler_init(self.device), "tiler_init")

@@ -9,6 +9,9 @@ reference runs the bins concurrently with ProcThreadPool, main.pas:4339):
   make_tiles_unique        MakeTilesUnique 2555-2612 (stable order: lowest index represents duplicates)
   make_tiles_unique_gpu    the same on the GPU (tiler_make_tiles_unique), any number of chunks in one call
   reindex_tiles            ReindexTiles 4483-4527 (UseCount desc, old index asc)
+  use_count_gpu / reindex_tiles_gpu / gather_tiles_gpu / remap_items_gpu
+                           btnReindexClick's counts 1208-1221, ReindexTiles and the TileMap remap (also
+                           FinishMergeTiles 3722-3734) on the GPU (tiler_tile_use_count, tiler_reindex_tiles, ...)
 The reload branch (ReloadPreviousTiling main.pas:4372-4470) snaps every active tile to its closest tile of a saved
 tileset instead; the matching runs on the GPU (tiler_tileset_load / tiler_tileset_match):
   write_tileset / read_tileset  the .gts file (main.pas:4359-4367 / 4420-4438)
@@ -230,6 +233,103 @@ def reindex_tiles(active, use_count):
     idx_map = np.full(np.asarray(active).shape[0], -1, np.int64)
     idx_map[order] = np.arange(order.size)
     return idx_map
+
+
+# ---- Reindex on the GPU (tiler_amd/csrc/reindex.hip): numpy arrays in and out, like make_tiles_unique_gpu ----
+def _vp(a):
+    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _items32(tile, who: str) -> np.ndarray:
+    """TileMap items as the library takes them: flat, contiguous int32 (a value that does not fit is refused)."""
+    t = np.asarray(tile)
+    if t.dtype.kind not in "iu":
+        raise ValueError(f"{who}: tilemap items must be integers")
+    if t.dtype != np.int32 and t.size and (int(t.min()) < -(1 << 31) or int(t.max()) >= (1 << 31)):
+        raise ValueError(f"{who}: a tilemap item does not fit 32 bits")
+    return np.ascontiguousarray(t, np.int32).ravel()
+
+
+def use_count_gpu(tile, T: int, use_count=None):
+    """btnReindexClick's UseCount / Active (main.pas:1208-1221) on the GPU (tiler_tile_use_count): (use_count int64 [T]
+    = np.bincount(tile, minlength=T), active uint8 [T] = use_count > 0).  use_count given ([T]): the items are
+    counted on top of a copy of it (another keyframe's or rank's count), and active is that of the sum."""
+    T = int(T)
+    if T < 0:
+        raise ValueError("use_count_gpu: T must not be negative")
+    items = _items32(tile, "use_count_gpu")
+    acc = use_count is not None
+    uc = np.array(use_count, np.int64, copy=True, order="C") if acc else np.zeros(T, np.int64)
+    if uc.shape != (T,):
+        raise ValueError("use_count_gpu: use_count must be [T]")
+    active = np.zeros(T, np.uint8)
+    check(load().tiler_tile_use_count(_vp(items), items.size, T, _vp(uc), _vp(active), int(acc)),
+          "tiler_tile_use_count")
+    return uc, active
+
+
+def reindex_tiles_gpu(active, use_count, return_order: bool = False):
+    """reindex_tiles on the GPU (tiler_reindex_tiles): the same idx_map; return_order: (idx_map, order), order[new] =
+    old over the active tiles."""
+    active = np.asarray(active)
+    use_count = np.asarray(use_count)
+    if active.ndim != 1 or use_count.shape != active.shape:
+        raise ValueError("reindex_tiles_gpu: active and use_count must be [T]")
+    active = np.ascontiguousarray(active != 0, np.uint8)
+    use_count = np.ascontiguousarray(use_count, np.int64)
+    T = active.shape[0]
+    idx_map = np.full(T, -1, np.int64)
+    order = np.full(T, -1, np.int64)
+    n = ctypes.c_int64(0)
+    check(load().tiler_reindex_tiles(_vp(active), _vp(use_count), T, _vp(idx_map), _vp(order), ctypes.byref(n)),
+          "tiler_reindex_tiles")
+    return (idx_map, order[:n.value]) if return_order else idx_map
+
+
+def gather_tiles_gpu(order, palpix=None, thm=None, tvm=None, dith_pal=None, use_count=None):
+    """The tile list in a new order on the GPU (tiler_gather_tiles): a[order] for every array given, as a tuple in
+    the order of the arguments (palpix [T][64] u8, thm / tvm [T] u8, dith_pal [T] i32, use_count [T] i64)."""
+    order = np.asarray(order)
+    if order.ndim != 1:
+        raise ValueError("gather_tiles_gpu: order must be [n]")
+    order = np.ascontiguousarray(order, np.int64)
+    given = [(palpix, np.uint8, (64,)), (thm, np.uint8, ()), (tvm, np.uint8, ()), (dith_pal, np.int32, ()),
+             (use_count, np.int64, ())]
+    T = None
+    ins, outs = [], []
+    for a, dt, tail in given:
+        if a is None:
+            ins.append(None)
+            outs.append(None)
+            continue
+        a = np.ascontiguousarray(a, dt)
+        if a.ndim != 1 + len(tail) or a.shape[1:] != tail or (T is not None and a.shape[0] != T):
+            raise ValueError("gather_tiles_gpu: the arrays must be [T] ([T][64] for palpix) with one T")
+        T = a.shape[0]
+        ins.append(a)
+        outs.append(np.zeros((order.size,) + tail, dt))
+    if T is None:
+        raise ValueError("gather_tiles_gpu: nothing to gather")
+    args = [x for pair in zip(ins, outs) for x in pair]
+    check(load().tiler_gather_tiles(_vp(order), order.size, *[_vp(x) for x in args], T), "tiler_gather_tiles")
+    return tuple(o for o in outs if o is not None)
+
+
+def remap_items_gpu(tile, map, keep_unmapped: bool = False):  # noqa: A002 (the issue's name for the argument)
+    """TileMap items through an index map on the GPU (tiler_remap_items), shape and dtype of `tile` kept:
+    map[tile] (ReindexTiles; -1 where the tile was dropped), or with keep_unmapped np.where(map[tile] >= 0,
+    map[tile], tile) (FinishMergeTiles)."""
+    tile = np.asarray(tile)
+    m = np.asarray(map)
+    if m.ndim != 1:
+        raise ValueError("remap_items_gpu: map must be [T]")
+    if m.dtype.kind not in "iu":
+        raise ValueError("remap_items_gpu: map must hold integers")
+    items = np.array(_items32(tile, "remap_items_gpu"), copy=True)
+    m = np.ascontiguousarray(m, np.int64)
+    check(load().tiler_remap_items(_vp(items), items.size, _vp(m), m.shape[0], int(bool(keep_unmapped))),
+          "tiler_remap_items")
+    return items.reshape(tile.shape).astype(tile.dtype, copy=False)
 
 
 # ---- the reload branch: .gts files and ReloadPreviousTiling (main.pas:4372-4470) ----

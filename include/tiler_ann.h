@@ -182,6 +182,17 @@ int tiler_psyv_batch(int n, const int32_t *rgb, int n_tiles, const uint8_t *palp
 int tiler_psyv_batch_dev(int n, const int32_t *rgb, const uint8_t *palpix, const int32_t *tile_of,
                          const int32_t *palettes, const int32_t *pal_of, const uint8_t *flags_per, int flags, int gamma,
                          double *out64, float *out32, void *stream);
+/* The same two with an explicit palette size: palettes[*][palsize], palsize 1..256 (the reference offers 2, 4, 8, 16,
+ * 32 and 64, cbxPalSize main.lfm:452-470).  tiler_psyv_batch[_dev] above mean palsize = 16 and run the same code; the
+ * size is an argument, not a process-wide setting, so encoders of different sizes share a process.  The host-buffer
+ * forms reject a tile byte >= palsize (the message names the first such tile); the _dev forms cannot report one and
+ * read colour 0 of the item's palette for it, never past the table. */
+int tiler_psyv_batch_ps(int n, const int32_t *rgb, int n_tiles, const uint8_t *palpix, const int32_t *tile_of,
+                        int n_palettes, int palsize, const int32_t *palettes, const int32_t *pal_of,
+                        const uint8_t *flags_per, int flags, int gamma, double *out64, float *out32);
+int tiler_psyv_batch_ps_dev(int n, const int32_t *rgb, const uint8_t *palpix, const int32_t *tile_of,
+                            const int32_t *palettes, int palsize, const int32_t *pal_of, const uint8_t *flags_per,
+                            int flags, int gamma, double *out64, float *out32, void *stream);
 /* Test hook (process-wide): palette-mode DCT descriptors (no wavelets, no LAB, per-item flags absent or mirrors
  * only) of min_items items or more are computed one lane per item, fewer one wave per item; 0 restores the default,
  * 32768.  Results are identical for every value.  0 / -1 (min_items < 0). */
@@ -219,6 +230,14 @@ ann_kdtree *tiler_prepare_frame_tiling_dev(ann_kdtree *global_ds, const int32_t 
                                            const uint8_t *d_thm, const uint8_t *d_tvm, int n_tiles,
                                            const int32_t *d_palettes, int n_palettes, int quality, const uint8_t *near,
                                            int use_wavelets, int gamma, void *stream, tiler_prepare_info *info);
+/* The same with d_palettes[n_palettes][palsize] (1..256); tiler_prepare_frame_tiling_dev means palsize = 16.  The
+ * 64-d rows of global_ds then hold values up to palsize - 1; the k = 8 preselection stays exact (integer rows). */
+ann_kdtree *tiler_prepare_frame_tiling_ps_dev(ann_kdtree *global_ds, const int32_t *d_item_tile,
+                                              const int32_t *d_item_pal, int64_t n_items, const uint8_t *d_palpix,
+                                              const uint8_t *d_thm, const uint8_t *d_tvm, int n_tiles,
+                                              const int32_t *d_palettes, int n_palettes, int palsize, int quality,
+                                              const uint8_t *near, int use_wavelets, int gamma, void *stream,
+                                              tiler_prepare_info *info);
 /* Same, every buffer in HBM, asynchronous on stream (the benchmarked path): no host synchronisation inside, every
  * data-dependent count (flat tiles, tier-2 / tier-3 queries) stays on the device. */
 int tiler_frame_tiling_dev(ann_kdtree *akd, const int32_t *d_rgb, int Q, int use_wavelets, int gamma,
@@ -234,6 +253,14 @@ int tiler_smooth_keyframe(int F, int Q, int32_t *tile, int32_t *tmpidx, int32_t 
 int tiler_smooth_keyframe_dev(int F, int Q, int32_t *d_tile, int32_t *d_tmpidx, int32_t *d_pal, uint8_t *d_hm,
                               uint8_t *d_vm, uint8_t *d_smoothed, const uint8_t *d_palpix, const int32_t *d_palettes,
                               double strength, void *stream);
+/* The same two with palettes[P][palsize] (1..256); the forms above mean palsize = 16.  The host form rejects a tile
+ * byte >= palsize, naming the first such tile; the _dev form reads colour 0 for it. */
+int tiler_smooth_keyframe_ps(int F, int Q, int32_t *tile, int32_t *tmpidx, int32_t *pal, uint8_t *hm, uint8_t *vm,
+                             uint8_t *smoothed, int T, const uint8_t *palpix, int P, int palsize,
+                             const int32_t *palettes, double strength);
+int tiler_smooth_keyframe_ps_dev(int F, int Q, int32_t *d_tile, int32_t *d_tmpidx, int32_t *d_pal, uint8_t *d_hm,
+                                 uint8_t *d_vm, uint8_t *d_smoothed, const uint8_t *d_palpix,
+                                 const int32_t *d_palettes, int palsize, double strength, void *stream);
 
 /* ---- GlobalTiling K-Modes (TKModes.ComputeKModes kmodes.pas:917-1060) ----
  * X[n][nattr] bytes; k clusters; start_point = -ANumInit (the DoKModes call, main.pas:4218); labels[n]
@@ -424,7 +451,7 @@ int tiler_frame_quality_dev(const int32_t *d_src, const int32_t *d_dst, int F, i
 
 /* ---- Dither step, per tile (FinishDitherTiles main.pas:2482-2544) -------------------------
  * For n frame tiles rgb[n][64] (0x00BBGGRR) and their keyframe palette pal_of[n] (DitheringPalIndex) out of
- * palettes[n_palettes][palsize] (PaletteRGB, palsize a power of two <= 16): DitherTile with Thomas Knoll mixing
+ * palettes[n_palettes][palsize] (PaletteRGB, palsize 1, 2, 4, 8, 16, 32 or 64): DitherTile with Thomas Knoll mixing
  * (the default, main.pas:1998-2055 / 1828-1875) then PrepareTileMirrors (main.pas:4049-4069) ->
  * palpix[n][64] palette indices in canonical orientation, hm/vm[n] (TTile.HMirror / VMirror).
  * Palette generation (yakmo k-means) and DitheringPalIndex selection are not part of this call.  0 / -1. */
@@ -436,7 +463,7 @@ int tiler_dither_tiles_dev(int n, const int32_t *d_rgb, const int32_t *d_pal_of,
 /* The same step with Yliluoma mixing instead (chkUseTK unchecked, main.lfm:272-282): DitherTile's other branch
  * (main.pas:2055-2067) with DeviseBestMixingPlanYliluoma (main.pas:1573-1826, the ASM_DBMP form the reference build
  * compiles), mixed_colors = FY2MixedColors (cbxYilMix: 1, 2, 4 (the form's default), 8, 16; here 1..64), palsize
- * 1..16 (any size).  Then PrepareTileMirrors as above.  0 / -1. */
+ * 1..16 (any size), 32 or 64.  Then PrepareTileMirrors as above.  0 / -1. */
 int tiler_dither_tiles_yliluoma(int n, const int32_t *rgb, const int32_t *pal_of, const int32_t *palettes,
                                 int n_palettes, int palsize, int mixed_colors, uint8_t *palpix, uint8_t *hm,
                                 uint8_t *vm);

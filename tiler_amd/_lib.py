@@ -99,11 +99,18 @@ _SIGS = {
                                  c_int, c_int, c_void_p, c_void_p]),
     "tiler_psyv_batch_dev": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                      c_void_p, c_void_p, c_void_p]),
+    "tiler_psyv_batch_ps": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                    c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "tiler_psyv_batch_ps_dev": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                        c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "tiler_ft_set_maps": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "tiler_ft_get_maps": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "tiler_prepare_frame_tiling_dev": (c_void_p, [c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p,
                                                   c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
                                                   c_void_p, P(PrepareInfo)]),
+    "tiler_prepare_frame_tiling_ps_dev": (c_void_p, [c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p,
+                                                     c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
+                                                     c_void_p, c_int, c_int, c_void_p, P(PrepareInfo)]),
     "tiler_frame_tiling": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p]),
     "tiler_frame_tiling_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
@@ -112,6 +119,10 @@ _SIGS = {
                                       c_void_p, c_int, c_void_p, c_double]),
     "tiler_smooth_keyframe_dev": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_double, c_void_p]),
+    "tiler_smooth_keyframe_ps": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_int, c_void_p, c_int, c_int, c_void_p, c_double]),
+    "tiler_smooth_keyframe_ps_dev": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_int, c_double, c_void_p]),
     "tiler_kmodes_medoids": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "tiler_kmodes_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                    c_void_p, c_void_p]),

@@ -672,11 +672,12 @@ int tiler_placement_plan(int ndev, const int64_t *bytes, int n, int32_t *dev_out
     return 0;
 }
 
-ann_kdtree *tiler_prepare_frame_tiling_dev(ann_kdtree *global_ds, const int32_t *d_item_tile,
-                                           const int32_t *d_item_pal, int64_t n_items, const uint8_t *d_palpix,
-                                           const uint8_t *d_thm, const uint8_t *d_tvm, int n_tiles,
-                                           const int32_t *d_palettes, int n_palettes, int quality, const uint8_t *near,
-                                           int use_wavelets, int gamma, void *stream, tiler_prepare_info *info) {
+ann_kdtree *tiler_prepare_frame_tiling_ps_dev(ann_kdtree *global_ds, const int32_t *d_item_tile,
+                                              const int32_t *d_item_pal, int64_t n_items, const uint8_t *d_palpix,
+                                              const uint8_t *d_thm, const uint8_t *d_tvm, int n_tiles,
+                                              const int32_t *d_palettes, int n_palettes, int palsize, int quality,
+                                              const uint8_t *near, int use_wavelets, int gamma, void *stream,
+                                              tiler_prepare_info *info) {
     if (!global_ds || !global_ds->ix || (n_items > 0 && (!d_item_tile || !d_item_pal)) || !d_palpix || !d_thm ||
         !d_tvm || !d_palettes) {
         set_error("tiler_prepare_frame_tiling_dev: invalid arguments");
@@ -702,8 +703,8 @@ ann_kdtree *tiler_prepare_frame_tiling_dev(ann_kdtree *global_ds, const int32_t 
         std::lock_guard<std::mutex> lk(gds->ix->mu);  // its k = 8 search scratch and the prepare scratch
         if (!gds->prep) gds->prep = new PrepScratch();
         t->ix = prepare_frame_tiling_dev(gds->ix, *gds->prep, d_item_tile, d_item_pal, (long)n_items, d_palpix, d_thm,
-                                         d_tvm, n_tiles, d_palettes, n_palettes, quality, near, use_wavelets, gamma, s,
-                                         &nd, &nc);
+                                         d_tvm, n_tiles, d_palettes, n_palettes, palsize, quality, near, use_wavelets,
+                                         gamma, s, &nd, &nc);
     }
     if (!t->ix || hipEventCreateWithFlags(&t->maps_ev, hipEventDisableTiming) != hipSuccess ||
         hipEventRecord(t->maps_ev, s) != hipSuccess) {
@@ -720,6 +721,16 @@ ann_kdtree *tiler_prepare_frame_tiling_dev(ann_kdtree *global_ds, const int32_t 
         info->candidates = nc;
     }
     return t;
+}
+
+ann_kdtree *tiler_prepare_frame_tiling_dev(ann_kdtree *global_ds, const int32_t *d_item_tile,
+                                           const int32_t *d_item_pal, int64_t n_items, const uint8_t *d_palpix,
+                                           const uint8_t *d_thm, const uint8_t *d_tvm, int n_tiles,
+                                           const int32_t *d_palettes, int n_palettes, int quality, const uint8_t *near,
+                                           int use_wavelets, int gamma, void *stream, tiler_prepare_info *info) {
+    return tiler_prepare_frame_tiling_ps_dev(global_ds, d_item_tile, d_item_pal, n_items, d_palpix, d_thm, d_tvm,
+                                             n_tiles, d_palettes, n_palettes, 16, quality, near, use_wavelets, gamma,
+                                             stream, info);
 }
 
 int ann_kdtree_search_multi_batch(ann_kdtree *t, const float *q, int nq, int k, float eps, int *idxs, float *errs) {
@@ -1166,9 +1177,9 @@ int tiler_kdtree_positions(ann_kdtree *t, int32_t *pos) {
     return kd_tree_positions(t->ix->kd, pos);
 }
 
-int tiler_psyv_batch_dev(int n, const int32_t *rgb, const uint8_t *palpix, const int32_t *tile_of,
-                         const int32_t *palettes, const int32_t *pal_of, const uint8_t *flags_per, int flags, int gamma,
-                         double *out64, float *out32, void *stream) {
+int tiler_psyv_batch_ps_dev(int n, const int32_t *rgb, const uint8_t *palpix, const int32_t *tile_of,
+                            const int32_t *palettes, int palsize, const int32_t *pal_of, const uint8_t *flags_per,
+                            int flags, int gamma, double *out64, float *out32, void *stream) {
     if (!ensure_init()) return -1;
     DevScope ds(ptr_device(rgb ? (const void *)rgb : (const void *)palpix));
     PsyvArgs a;
@@ -1177,6 +1188,7 @@ int tiler_psyv_batch_dev(int n, const int32_t *rgb, const uint8_t *palpix, const
     a.palpix = palpix;
     a.tile_of = tile_of;
     a.palettes = palettes;
+    a.palsize = palsize;
     a.pal_of = pal_of;
     a.flags_per = flags_per;
     a.flags = flags;
@@ -1186,12 +1198,26 @@ int tiler_psyv_batch_dev(int n, const int32_t *rgb, const uint8_t *palpix, const
     return launch_psyv(a, (hipStream_t)stream);
 }
 
+int tiler_psyv_batch_dev(int n, const int32_t *rgb, const uint8_t *palpix, const int32_t *tile_of,
+                         const int32_t *palettes, const int32_t *pal_of, const uint8_t *flags_per, int flags, int gamma,
+                         double *out64, float *out32, void *stream) {
+    return tiler_psyv_batch_ps_dev(n, rgb, palpix, tile_of, palettes, 16, pal_of, flags_per, flags, gamma, out64, out32,
+                                   stream);
+}
+
+int tiler_psyv_batch_ps(int n, const int32_t *rgb, int n_tiles, const uint8_t *palpix, const int32_t *tile_of,
+                        int n_palettes, int palsize, const int32_t *palettes, const int32_t *pal_of,
+                        const uint8_t *flags_per, int flags, int gamma, double *out64, float *out32) {
+    if (!ensure_init()) return -1;
+    return psyv_batch_host(n, rgb, n_tiles, palpix, tile_of, n_palettes, palsize, palettes, pal_of, flags_per, flags,
+                           gamma, out64, out32);
+}
+
 int tiler_psyv_batch(int n, const int32_t *rgb, int n_tiles, const uint8_t *palpix, const int32_t *tile_of,
                      int n_palettes, const int32_t *palettes, const int32_t *pal_of, const uint8_t *flags_per,
                      int flags, int gamma, double *out64, float *out32) {
-    if (!ensure_init()) return -1;
-    return psyv_batch_host(n, rgb, n_tiles, palpix, tile_of, n_palettes, palettes, pal_of, flags_per, flags, gamma, out64,
-                           out32);
+    return tiler_psyv_batch_ps(n, rgb, n_tiles, palpix, tile_of, n_palettes, 16, palettes, pal_of, flags_per, flags,
+                               gamma, out64, out32);
 }
 
 int tiler_debug_psyv_lane_items(int64_t min_items) { return psyv_lane_items_debug((long)min_items); }
@@ -1312,20 +1338,33 @@ int tiler_frame_tiling(ann_kdtree *t, const int32_t *rgb, int Q, int use_wavelet
     return 0;
 }
 
+int tiler_smooth_keyframe_ps(int F, int Q, int32_t *tile, int32_t *tmpidx, int32_t *pal, uint8_t *hm, uint8_t *vm,
+                             uint8_t *smoothed, int T, const uint8_t *palpix, int P, int palsize,
+                             const int32_t *palettes, double strength) {
+    if (!ensure_init()) return -1;
+    return smooth_keyframe_host(F, Q, tile, tmpidx, pal, hm, vm, smoothed, T, palpix, P, palettes, palsize, strength);
+}
+
 int tiler_smooth_keyframe(int F, int Q, int32_t *tile, int32_t *tmpidx, int32_t *pal, uint8_t *hm, uint8_t *vm,
                           uint8_t *smoothed, int T, const uint8_t *palpix, int P, const int32_t *palettes,
                           double strength) {
+    return tiler_smooth_keyframe_ps(F, Q, tile, tmpidx, pal, hm, vm, smoothed, T, palpix, P, 16, palettes, strength);
+}
+
+int tiler_smooth_keyframe_ps_dev(int F, int Q, int32_t *d_tile, int32_t *d_tmpidx, int32_t *d_pal, uint8_t *d_hm,
+                                 uint8_t *d_vm, uint8_t *d_smoothed, const uint8_t *d_palpix,
+                                 const int32_t *d_palettes, int palsize, double strength, void *stream) {
     if (!ensure_init()) return -1;
-    return smooth_keyframe_host(F, Q, tile, tmpidx, pal, hm, vm, smoothed, T, palpix, P, palettes, strength);
+    DevScope ds(ptr_device(d_tile));
+    return smooth_keyframe_dev(F, Q, d_tile, d_tmpidx, d_pal, d_hm, d_vm, d_smoothed, d_palpix, d_palettes, palsize,
+                               strength, (hipStream_t)stream);
 }
 
 int tiler_smooth_keyframe_dev(int F, int Q, int32_t *d_tile, int32_t *d_tmpidx, int32_t *d_pal, uint8_t *d_hm,
                               uint8_t *d_vm, uint8_t *d_smoothed, const uint8_t *d_palpix, const int32_t *d_palettes,
                               double strength, void *stream) {
-    if (!ensure_init()) return -1;
-    DevScope ds(ptr_device(d_tile));
-    return smooth_keyframe_dev(F, Q, d_tile, d_tmpidx, d_pal, d_hm, d_vm, d_smoothed, d_palpix, d_palettes, strength,
-                               (hipStream_t)stream);
+    return tiler_smooth_keyframe_ps_dev(F, Q, d_tile, d_tmpidx, d_pal, d_hm, d_vm, d_smoothed, d_palpix, d_palettes, 16,
+                                        strength, stream);
 }
 
 int tiler_dither_tiles(int n, const int32_t *rgb, const int32_t *pal_of, const int32_t *palettes, int n_palettes,

@@ -10,7 +10,11 @@
 // ranges commute, so the visiting order does not change the result), and reads entry cDitheringMap[y*8+x].  The quadrant sums and
 // the flip of PrepareTileMirrors are wave reductions and one lane permutation.
 // Integer ranges: |e| <= 63*255, so |t| <= 255 + 1445 and every ColorCompare term fits int32
-// (3*13*1723^2 + 32*1723^2 < 2^31): int32 arithmetic gives the reference's Int64 results exactly.
+// (3*13*1723^2 + 32*1723^2 < 2^31): int32 arithmetic gives the reference's Int64 results exactly.  None of this
+// depends on the palette size: the 63 is the list length (64 diffusion steps) and the 255 the 8-bit components, so
+// the same bounds hold for the 32- and 64-entry kernels below.
+// Palette sizes: 1..16 run dither_tk_kernel / dither_yl_kernel (palette in registers); 32 and 64 run the _big
+// kernels (palette constants wave-uniform in LDS, a loop over entries), chosen on the host.
 // The reference's colour cache (CountCache/ListCache) only memoises lists per colour: not needed here.
 #include <string>
 
@@ -26,6 +30,7 @@ __constant__ uint8_t c_dither_map[64] = {  // cDitheringMap main.pas:46-55
 
 constexpr int DT_WAVES = 4;       // tiles per workgroup
 constexpr int DT_MAXPAL = 16;     // palette entries held in registers
+constexpr int DT_BIGPAL = 64;     // palette entries the _big kernels hold in LDS (sizes 32 and 64)
 constexpr int DT_STACK = 8;       // pending quicksort ranges per lane (larger side stacked: <= log2 64)
 
 // The reference QuickSort (kmodes.pas:89-136) of this lane's list entries [0, last] ([entry][lane] bytes in LDS) by
@@ -245,6 +250,117 @@ __global__ __launch_bounds__(64 * DT_WAVES) void dither_tk_kernel(const int32_t 
     tile_mirrors_store(px, lane, tile, palpix, hm, vm);
 }
 
+// Thomas Knoll for 32 and 64 entries.  The same plan as dither_tk_kernel, entry by entry in the same order, but five
+// register arrays of 64 would spill: the per-entry constants (r, g, b, 13|p|^2 and LumaPal's quotient / remainder)
+// sit in LDS, read at a wave-uniform index (one broadcast read per entry), and the compare loop is a loop.  The list
+// histogram is 64 counters of up to 64: a byte each in the lane's [entry][lane] column of s_list -- the no-tie path
+// needs no list and the tie path no histogram, so the two share the 4 KiB.
+__global__ __launch_bounds__(64 * DT_WAVES) void dither_tk_big_kernel(const int32_t *__restrict__ rgb,
+                                                                      const int32_t *__restrict__ pal_of,
+                                                                      const int32_t *__restrict__ palettes,
+                                                                      int n_palettes, int palsize, int n,
+                                                                      uint8_t *__restrict__ palpix,
+                                                                      uint8_t *__restrict__ hm,
+                                                                      uint8_t *__restrict__ vm) {
+    __shared__ uint8_t s_list[DT_WAVES][64 * 64];           // [entry][lane]: list (equal lumas) or histogram
+    __shared__ uint16_t s_stk[DT_WAVES][DT_STACK * 64];     // [depth][lane]: first | last << 8
+    __shared__ int4 s_pal[DT_WAVES][DT_BIGPAL];             // pr, pg, pb, pc = 13 |p|^2
+    __shared__ int2 s_lq[DT_WAVES][DT_BIGPAL];              // la, lb: LumaPal = 10000 la + lb
+    __shared__ int s_luma[DT_WAVES][DT_BIGPAL];             // LumaPal of the tile's palette
+    __shared__ int s_order[DT_WAVES][DT_BIGPAL];            // entries in luma order (no-tie path)
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int tile = blockIdx.x * DT_WAVES + w;
+    if (tile >= n) return;
+    const int p = pal_of[tile];
+    uint8_t *list = s_list[w];
+    if (p < 0 || p >= n_palettes) {  // invalid input (the host entry rejects it): defined output, no fault
+        palpix[(long)tile * 64 + lane] = 0;
+        if (lane == 0) hm[tile] = vm[tile] = 0;
+        return;
+    }
+    // PreparePlan and the compare-loop constants of dither_tk_kernel, one entry per lane (palsize <= 64 lanes)
+    if (lane < palsize) {
+        const int c = palettes[(long)p * palsize + lane];
+        const int r = c & 0xff, g = (c >> 8) & 0xff, b = (c >> 16) & 0xff;
+        const int pl = r * 2126 + g * 7152 + b * 722;
+        const int qa = pl / 10000;
+        s_pal[w][lane] = make_int4(r, g, b, 13 * (r * r + g * g + b * b));
+        s_lq[w][lane] = make_int2(qa, pl - qa * 10000);
+        s_luma[w][lane] = pl;
+    }
+#pragma unroll
+    for (int k = 0; k < 16; k++) reinterpret_cast<uint32_t *>(list)[k * 64 + lane] = 0u;  // the histogram
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    auto luma_of = [&](int v) { return s_luma[w][v]; };  // LumaPal[v] (PlanCompareLuma)
+    int rank = 0;
+    bool tie = false;
+    if (lane < palsize) {
+        const int my = luma_of(lane);
+        for (int j = 0; j < palsize; j++) {
+            const int o = luma_of(j);
+            rank += o < my ? 1 : 0;
+            tie |= (o == my) && j != lane;
+        }
+    }
+    const bool any_tie = __ballot(tie) != 0;
+    // DeviseBestMixingPlanThomasKnoll for this lane's colour
+    const int col = rgb[(long)tile * 64 + lane];
+    const int s0 = col & 0xff, s1 = (col >> 8) & 0xff, s2 = (col >> 16) & 0xff;
+    int e0 = 0, e1 = 0, e2 = 0;
+    for (int c = 0; c < 64; c++) {
+        const int t0 = s0 + (e0 * 9) / 100, t1 = s1 + (e1 * 9) / 100, t2 = s2 + (e2 * 9) / 100;
+        const int l1 = t0 * 2126 + t1 * 7152 + t2 * 722;
+        const int A = (l1 >= 0 ? l1 : l1 - 9999) / 10000, B = l1 - A * 10000;  // floor division, 0 <= B < 10000
+        int least = 0x7fffffff, chosen = c & (palsize - 1);
+#pragma unroll 4
+        for (int i = 0; i < palsize; i++) {
+            const int4 e = s_pal[w][i];  // uniform address: one broadcast read
+            const int2 q = s_lq[w][i];
+            const int tp = __mul24(t0, e.x) + __mul24(t1, e.y) + __mul24(t2, e.z);
+            const int fl = (A - q.x) - (B < q.y ? 1 : 0);
+            const int ld = fl + ((fl < 0 && B != q.y) ? 1 : 0);  // trunc((l1 - LumaPal_i) / 10000)
+            const int pen = e.w - 26 * tp + ((ld * ld) << 5);    // ColorCompare - 13*|t|^2
+            if (pen < least) {
+                least = pen;
+                chosen = i;
+            }
+        }
+        if (any_tie)
+            list[c * 64 + lane] = (uint8_t)chosen;  // only the exact sort needs the list
+        else
+            list[chosen * 64 + lane]++;             // this lane's count of entry `chosen` (<= 64)
+        const int4 ce = s_pal[w][chosen];
+        e0 += s0 - ce.x;
+        e1 += s1 - ce.y;
+        e2 += s2 - ce.z;
+    }
+    int px;
+    if (!any_tie) {
+        if (lane < palsize) s_order[w][rank] = lane;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const int want = c_dither_map[lane];
+        int acc = 0;
+        px = 0;
+        bool found = false;
+        for (int r = 0; r < palsize; r++) {
+            const int idx = s_order[w][r];
+            acc += list[idx * 64 + lane];
+            if (!found && acc > want) {
+                px = idx;
+                found = true;
+            }
+        }
+    } else {  // QuickSort (kmodes.pas:89-136), only for palettes with equal lumas
+        lane_quicksort(list, s_stk[w], lane, 63, luma_of);
+        px = list[c_dither_map[lane] * 64 + lane];
+    }
+    tile_mirrors_store(px, lane, tile, palpix, hm, vm);
+}
+
 // DitherTile's Yliluoma branch (chkUseTK unchecked, main.pas:2055-2067): per pixel the mixing plan of
 // DeviseBestMixingPlanYliluoma in the form the reference build runs -- main.pas:5 defines ASM_DBMP, so on x86-64 the
 // SSE block (main.pas:1602-1752) is the algorithm: lanes (r, g, b, luma) of sum += add, add += 1 per tried count t,
@@ -353,15 +469,98 @@ __global__ __launch_bounds__(64 * DT_WAVES) void dither_yl_kernel(const int32_t 
     tile_mirrors_store(px, lane, tile, palpix, hm, vm);
 }
 
+// Yliluoma for 32 and 64 entries: dither_yl_kernel with Y2Palette's rows (r, g, b, luma div cLumaDiv) in LDS, read at
+// a wave-uniform index per tried entry and at the lane's own index for the chosen one.
+__global__ __launch_bounds__(64 * DT_WAVES) void dither_yl_big_kernel(const int32_t *__restrict__ rgb,
+                                                                      const int32_t *__restrict__ pal_of,
+                                                                      const int32_t *__restrict__ palettes,
+                                                                      int n_palettes, int palsize, int mixed, int n,
+                                                                      uint8_t *__restrict__ palpix,
+                                                                      uint8_t *__restrict__ hm,
+                                                                      uint8_t *__restrict__ vm) {
+    __shared__ uint8_t s_list[DT_WAVES][DY_LIST * 64];      // [entry][lane]
+    __shared__ uint16_t s_stk[DT_WAVES][DT_STACK * 64];     // [depth][lane]: first | last << 8
+    __shared__ uint4 s_y[DT_WAVES][DT_BIGPAL];              // Y2Palette rows
+    __shared__ int s_luma[DT_WAVES][DT_BIGPAL];             // LumaPal of the tile's palette
+    __shared__ uint32_t s_inv[DY_LIST + 1];                 // gVecInv rows: 65536 div t (main.pas:610-611)
+    for (int t = threadIdx.x; t <= DY_LIST; t += blockDim.x) s_inv[t] = t ? 65536u / (uint32_t)t : 0u;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int tile = blockIdx.x * DT_WAVES + w;
+    if (tile >= n) return;
+    const int p = pal_of[tile];
+    uint8_t *list = s_list[w];
+    if (p < 0 || p >= n_palettes) {  // invalid input (the host entry rejects it): defined output, no fault
+        palpix[(long)tile * 64 + lane] = 0;
+        if (lane == 0) hm[tile] = vm[tile] = 0;
+        return;
+    }
+    if (lane < palsize) {
+        const int c = palettes[(long)p * palsize + lane];
+        const uint32_t r = c & 0xff, g = (c >> 8) & 0xff, b = (c >> 16) & 0xff;
+        const uint32_t pl = r * 2126u + g * 7152u + b * 722u;
+        s_y[w][lane] = make_uint4(r, g, b, pl / 10000u);
+        s_luma[w][lane] = (int)pl;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int col = rgb[(long)tile * 64 + lane];
+    const uint32_t x0 = col & 0xff, x1 = (col >> 8) & 0xff, x2 = (col >> 16) & 0xff;
+    const uint32_t x3 = (x0 * 2126u + x1 * 7152u + x2 * 722u) / 10000u;
+    uint32_t so0 = 0, so1 = 0, so2 = 0, so3 = 0;
+    int pc = 0;
+    while (pc < mixed) {
+        const int mt = pc == 0 ? 1 : pc;
+        uint32_t least = 0xffffffffu;  // every pen < 2^32 beats the asm's initial 2^63 - 1: the first one is taken
+        bool any = false;
+        int chosen = 0, chosen_t = pc + 1;
+        for (int i = 0; i < palsize; i++) {
+            uint32_t s0 = so0, s1 = so1, s2 = so2, s3 = so3;
+            const uint4 y = s_y[w][i];  // uniform address: one broadcast read
+            uint32_t a0 = y.x, a1 = y.y, a2 = y.z, a3 = y.w;
+            for (int t = pc + 1; t <= pc + mt; t++) {
+                s0 += a0; s1 += a1; s2 += a2; s3 += a3;
+                a0 += 1u; a1 += 1u; a2 += 1u; a3 += 1u;
+                const uint32_t inv = s_inv[t];
+                const uint32_t d0 = ((inv * s0) >> 16) - x0, d1 = ((inv * s1) >> 16) - x1;
+                const uint32_t d2 = ((inv * s2) >> 16) - x2, d3 = ((inv * s3) >> 16) - x3;
+                const uint32_t pen = (d0 * d0) * 13u + (d1 * d1) * 13u + (d2 * d2) * 13u + (d3 * d3) * 32u;
+                if (!any || pen < least) {
+                    any = true;
+                    least = pen;
+                    chosen = i;
+                    chosen_t = t;
+                }
+            }
+        }
+        const int amount = min(chosen_t - pc, 256 - pc);
+        for (int k = 0; k < amount; k++) list[(pc + k) * 64 + lane] = (uint8_t)chosen;
+        pc += amount;
+        const uint4 cy = s_y[w][chosen];
+        so0 += cy.x * (uint32_t)amount;
+        so1 += cy.y * (uint32_t)amount;
+        so2 += cy.z * (uint32_t)amount;
+        so3 += cy.w * (uint32_t)amount;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    auto luma_of = [&](int v) { return s_luma[w][v]; };  // LumaPal[v] (PlanCompareLuma)
+    lane_quicksort(list, s_stk[w], lane, pc - 1, luma_of);
+    const int px = list[((c_dither_map[lane] * pc) >> 6) * 64 + lane];
+    tile_mirrors_store(px, lane, tile, palpix, hm, vm);
+}
+
 static bool dither_args_ok(int n, const void *rgb, const void *pal_of, const void *palettes, int n_palettes,
                            int palsize, int mixed, const void *palpix, const void *hm, const void *vm) {
-    if (n < 0 || n_palettes <= 0 || palsize <= 0 || palsize > DT_MAXPAL ||
-        (n > 0 && (!rgb || !pal_of || !palettes || !palpix || !hm || !vm))) {
-        set_error("dither: invalid arguments (palette size 1..16)");
+    const bool size_ok = (palsize >= 1 && palsize <= DT_MAXPAL) || palsize == 32 || palsize == DT_BIGPAL;
+    if (n < 0 || n_palettes <= 0 || !size_ok || (n > 0 && (!rgb || !pal_of || !palettes || !palpix || !hm || !vm))) {
+        set_error("dither: invalid arguments (palette size 1..16, 32 or 64)");
         return false;
     }
     if (mixed == 0 && (palsize & (palsize - 1))) {
-        set_error("dither: invalid arguments (Thomas Knoll mixing: palette size a power of two <= 16)");
+        set_error("dither: invalid arguments (Thomas Knoll mixing: palette size 1, 2, 4, 8, 16, 32 or 64)");
         return false;
     }
     if (mixed < 0 || mixed > DY_MAXMIX) {
@@ -377,7 +576,15 @@ int dither_tiles_dev(int n, const int32_t *d_rgb, const int32_t *d_pal_of, const
     if (!dither_args_ok(n, d_rgb, d_pal_of, d_palettes, n_palettes, palsize, mixed, d_palpix, d_hm, d_vm)) return -1;
     if (n == 0) return 0;
     KTimer tm("dither", stream);
-    if (mixed == 0)
+    const dim3 grid((n + DT_WAVES - 1) / DT_WAVES), block(64 * DT_WAVES);
+    if (palsize > DT_MAXPAL) {  // 32 or 64 entries (dither_args_ok): the palette in LDS
+        if (mixed == 0)
+            hipLaunchKernelGGL(dither_tk_big_kernel, grid, block, 0, stream, d_rgb, d_pal_of, d_palettes, n_palettes,
+                               palsize, n, d_palpix, d_hm, d_vm);
+        else
+            hipLaunchKernelGGL(dither_yl_big_kernel, grid, block, 0, stream, d_rgb, d_pal_of, d_palettes, n_palettes,
+                               palsize, mixed, n, d_palpix, d_hm, d_vm);
+    } else if (mixed == 0)
         hipLaunchKernelGGL(dither_tk_kernel, dim3((n + DT_WAVES - 1) / DT_WAVES), dim3(64 * DT_WAVES), 0, stream, d_rgb,
                            d_pal_of, d_palettes, n_palettes, palsize, n, d_palpix, d_hm, d_vm);
     else

@@ -194,10 +194,14 @@ static int bm_scan(const unsigned *bits, long nwords, PrepScratch &s, int *total
 NNIndex *prepare_frame_tiling_dev(NNIndex *global, PrepScratch &s, const int32_t *d_item_tile,
                                   const int32_t *d_item_pal, long n_items, const uint8_t *d_palpix,
                                   const uint8_t *d_thm, const uint8_t *d_tvm, int T, const int32_t *d_palettes, int P,
-                                  int quality, const uint8_t *h_near, int use_wavelets, int gamma, hipStream_t stream,
+                                  int palsize, int quality, const uint8_t *h_near, int use_wavelets, int gamma, hipStream_t stream,
                                   long *n_distinct, long *n_cand) {
     if (!global || global->d != 64 || !global->d_tr_tile || !global->d_tr_attr) {
         set_error("prepare_frame_tiling: the global dataset must be PrepareGlobalFT's 64-d rows with maps set");
+        return nullptr;
+    }
+    if (!psyv_palsize_ok(palsize)) {
+        set_error("prepare_frame_tiling: palette size must be 1..256");
         return nullptr;
     }
     if (T <= 0 || P <= 0 || n_items < 0 || (long)P * T * 4 >= (1L << 31) || quality < 0 || quality > 2 ||
@@ -282,6 +286,7 @@ NNIndex *prepare_frame_tiling_dev(NNIndex *global, PrepScratch &s, const int32_t
     pa.palpix = d_palpix;
     pa.tile_of = s.tile_of;
     pa.palettes = d_palettes;
+    pa.palsize = palsize;
     pa.pal_of = s.pal_of;
     pa.flags_per = s.flags;
     pa.flags_per_mirrors_only = true;

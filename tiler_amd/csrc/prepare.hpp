@@ -29,11 +29,11 @@ void prep_scratch_free(PrepScratch *s);
 // The keyframe's search index (with its TRTo* maps) from its tilemap items: distinct (PalIdx, GlobalTileIndex)
 // -> k = 8 preselection in the global dataset `global` (PrepareGlobalFT's handle, maps set) -> used[P][T][4]
 // (UseOne: results of equal err after the first skipped; Fast: own palette, Medium: near[][], Slow: all) ->
-// candidates in DoPsyV order -> descriptors -> index.  Synchronises `stream` once (the candidate count).
+// candidates in DoPsyV order -> descriptors (d_palettes [P][palsize]) -> index.  Synchronises `stream` once (the candidate count).
 NNIndex *prepare_frame_tiling_dev(NNIndex *global, PrepScratch &s, const int32_t *d_item_tile,
                                   const int32_t *d_item_pal, long n_items, const uint8_t *d_palpix,
                                   const uint8_t *d_thm, const uint8_t *d_tvm, int T, const int32_t *d_palettes, int P,
-                                  int quality, const uint8_t *h_near, int use_wavelets, int gamma, hipStream_t stream,
+                                  int palsize, int quality, const uint8_t *h_near, int use_wavelets, int gamma, hipStream_t stream,
                                   long *n_distinct, long *n_cand);
 
 }  // namespace tiler

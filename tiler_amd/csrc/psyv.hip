@@ -6,8 +6,9 @@
 //   - RGBToYUV (main.pas:2656-2679) with r/255 and gGammaCorLut taken from a host-built LUT;
 //   - WaveletGS (main.pas:2805-2840): 3 Haar levels, rows then columns, neighbours via ds_bpermute;
 //   - DCT branch (main.pas:3075-3175): sequential 64-term sums against the host-built gDCTLut.
-// HBM traffic per tile: 256 B in (RGB) or 64 B + 64 B palette, 768 B (fp32) / 1536 B (fp64) out.
+// HBM traffic per tile: 256 B in (RGB) or 64 B + the palette (4 B x palsize), 768 B (fp32) / 1536 B (fp64) out.
 #include <atomic>
+#include <string>
 
 #include "psyv.hpp"
 #include "psyv_dev.hpp"
@@ -31,7 +32,8 @@ __global__ __launch_bounds__(256) void psyv_kernel(PsyvArgs a) {
         if (f & PSYV_FROM_PAL) {
             const long t = a.tile_of ? a.tile_of[i] : i;
             const long p = a.pal_of ? a.pal_of[i] : 0;
-            col = a.palettes[p * 16 + a.palpix[t * 64 + src]];
+            const int v = a.palpix[t * 64 + src];
+            col = a.palettes[p * a.palsize + (v < a.palsize ? v : 0)];
         } else {
             col = a.rgb[i * 64 + src];
         }
@@ -146,9 +148,12 @@ __global__ __launch_bounds__(64) void psyv_dct_items_kernel(PsyvArgs a) {
     const long t = a.tile_of ? a.tile_of[ii] : ii;
     const long p = a.pal_of ? a.pal_of[ii] : 0;
     const uint8_t *px = a.palpix + t * 64;
-    const int32_t *pal = a.palettes + p * 16;
+    const int32_t *pal = a.palettes + p * a.palsize;
 #pragma unroll 8
-    for (int k = 0; k < 64; k++) cols[lane][k] = pal[px[k ^ m]];
+    for (int k = 0; k < 64; k++) {
+        const int v = px[k ^ m];
+        cols[lane][k] = pal[v < a.palsize ? v : 0];
+    }
     const double *__restrict__ glut = a.gamma_lut + 256 * (a.gamma + 1);
     const bool qw = (f & PSYV_QWEIGHT) != 0;
 #pragma unroll 1
@@ -203,6 +208,10 @@ int launch_psyv(PsyvArgs args, hipStream_t stream) {
         set_error("psyv: gamma must be -1, 0 or 1");
         return -1;
     }
+    if (!psyv_palsize_ok(args.palsize)) {
+        set_error("psyv: palette size must be 1..256");
+        return -1;
+    }
     KTimer tm("psyv", stream);
     if (args.rootbox && !(args.rgb && !args.flags_per && args.flags == PSYV_WAVELETS)) {
         set_error("psyv: the fused root-box output exists on the RGB Haar query path only");
@@ -231,9 +240,16 @@ int launch_psyv(PsyvArgs args, hipStream_t stream) {
     return 0;
 }
 
+long first_bad_tile(const uint8_t *palpix, long n_tiles, int palsize) {
+    if (palsize >= 256) return -1;
+    for (long i = 0; i < n_tiles * 64; i++)
+        if (palpix[i] >= palsize) return i / 64;
+    return -1;
+}
+
 int psyv_batch_host(int n, const int32_t *rgb, int n_tiles, const uint8_t *palpix, const int32_t *tile_of,
-                    int n_palettes, const int32_t *palettes, const int32_t *pal_of, const uint8_t *flags_per, int flags,
-                    int gamma, double *out64, float *out32) {
+                    int n_palettes, int palsize, const int32_t *palettes, const int32_t *pal_of,
+                    const uint8_t *flags_per, int flags, int gamma, double *out64, float *out32) {
     if (n < 0) {
         set_error("psyv: n < 0");
         return -1;
@@ -244,13 +260,26 @@ int psyv_batch_host(int n, const int32_t *rgb, int n_tiles, const uint8_t *palpi
         set_error("psyv: missing input buffer");
         return -1;
     }
+    if (from_pal) {
+        if (!psyv_palsize_ok(palsize)) {
+            set_error("psyv: palette size must be 1..256");
+            return -1;
+        }
+        const long bad = first_bad_tile(palpix, n_tiles, palsize);
+        if (bad >= 0) {
+            set_error("psyv: tile " + std::to_string(bad) + " has a palette index >= the palette size " +
+                      std::to_string(palsize));
+            return -1;
+        }
+    }
     HostStage s("psyv");
     PsyvArgs a;
     a.n = n;
+    a.palsize = palsize;
     a.rgb = s.in(rgb, (size_t)n * 64);
     if (from_pal) {
         a.palpix = s.in(palpix, (size_t)n_tiles * 64);
-        a.palettes = s.in(palettes, (size_t)n_palettes * 16);
+        a.palettes = s.in(palettes, (size_t)n_palettes * palsize);
     }
     a.tile_of = s.in(tile_of, (size_t)n);
     a.pal_of = s.in(pal_of, (size_t)n);

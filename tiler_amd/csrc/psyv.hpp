@@ -11,7 +11,8 @@ struct PsyvArgs {
     const int32_t *rgb = nullptr;       // [n][64]
     const uint8_t *palpix = nullptr;    // [T][64]
     const int32_t *tile_of = nullptr;   // [n] or null (identity)
-    const int32_t *palettes = nullptr;  // [P][16]
+    const int32_t *palettes = nullptr;  // [P][palsize]
+    int palsize = 16;                   // palette stride (FTilePaletteSize); a tile byte >= palsize reads colour 0
     const int32_t *pal_of = nullptr;    // [n] or null (palette 0)
     const uint8_t *flags_per = nullptr; // [n] or null
     bool flags_per_mirrors_only = false; // flags_per holds only PSYV_HMIRROR / PSYV_VMIRROR bits (caller's promise)
@@ -33,10 +34,16 @@ struct PsyvArgs {
 int launch_psyv(PsyvArgs args, hipStream_t stream);
 int psyv_lane_items_debug(long min_items);  // tiler_debug_psyv_lane_items
 
-// host-buffer form (tiler_psyv_batch): palpix [n_tiles][64] and palettes [n_palettes][16] are read only when the
-// descriptors come from palettes (PSYV_FROM_PAL or flags_per); out64 / out32: either or both
+// host-buffer form (tiler_psyv_batch[_ps]): palpix [n_tiles][64] and palettes [n_palettes][palsize] are read only
+// when the descriptors come from palettes (PSYV_FROM_PAL or flags_per); a tile byte >= palsize is an error;
+// out64 / out32: either or both
 int psyv_batch_host(int n, const int32_t *rgb, int n_tiles, const uint8_t *palpix, const int32_t *tile_of,
-                    int n_palettes, const int32_t *palettes, const int32_t *pal_of, const uint8_t *flags_per, int flags,
-                    int gamma, double *out64, float *out32);
+                    int n_palettes, int palsize, const int32_t *palettes, const int32_t *pal_of,
+                    const uint8_t *flags_per, int flags, int gamma, double *out64, float *out32);
+
+// the palette sizes the descriptor paths take (cbxPalSize offers 2..64; the tile bytes allow 256)
+inline bool psyv_palsize_ok(int palsize) { return palsize >= 1 && palsize <= 256; }
+// first tile of palpix[n_tiles][64] with a byte >= palsize, or -1
+long first_bad_tile(const uint8_t *palpix, long n_tiles, int palsize);
 
 }  // namespace tiler

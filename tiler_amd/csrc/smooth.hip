@@ -225,8 +225,12 @@ __global__ __launch_bounds__(64) void smooth_chain_coop_kernel(SmoothArgs a) {
 }
 
 int smooth_keyframe_dev(int F, int Q, int32_t *tile, int32_t *tmpidx, int32_t *pal, uint8_t *hm, uint8_t *vm,
-                        uint8_t *sm, const uint8_t *palpix, const int32_t *palettes, double strength,
+                        uint8_t *sm, const uint8_t *palpix, const int32_t *palettes, int palsize, double strength,
                         hipStream_t stream) {
+    if (!psyv_palsize_ok(palsize)) {
+        set_error("smooth: palette size must be 1..256");
+        return -1;
+    }
     if (F <= 1 || Q <= 0) return 0;
     const long n = (long)F * Q;
     long cap = 1024;
@@ -269,6 +273,7 @@ int smooth_keyframe_dev(int F, int Q, int32_t *tile, int32_t *tmpidx, int32_t *p
         pa.palpix = palpix;
         pa.tile_of = h.u_tile;
         pa.palettes = palettes;
+        pa.palsize = palsize;
         pa.pal_of = h.u_pal;
         pa.flags_per = h.u_flags;
         pa.flags_per_mirrors_only = true;
@@ -296,7 +301,7 @@ int smooth_keyframe_dev(int F, int Q, int32_t *tile, int32_t *tmpidx, int32_t *p
 }
 
 int smooth_keyframe_host(int F, int Q, int32_t *tile, int32_t *tmpidx, int32_t *pal, uint8_t *hm, uint8_t *vm,
-                         uint8_t *smoothed, int T, const uint8_t *palpix, int P, const int32_t *palettes,
+                         uint8_t *smoothed, int T, const uint8_t *palpix, int P, const int32_t *palettes, int palsize,
                          double strength) {
     if (F < 0 || Q < 0 || T < 0 || P < 0 || (F * (long)Q > 0 && (!tile || !pal || !hm || !vm || !smoothed))) {
         set_error("smooth: invalid arguments");
@@ -305,6 +310,16 @@ int smooth_keyframe_host(int F, int Q, int32_t *tile, int32_t *tmpidx, int32_t *
     if (F <= 1 || Q == 0) return 0;
     if (!palpix || !palettes || T <= 0 || P <= 0) {
         set_error("smooth: tiles / palettes missing");
+        return -1;
+    }
+    if (!psyv_palsize_ok(palsize)) {
+        set_error("smooth: palette size must be 1..256");
+        return -1;
+    }
+    const long bad = first_bad_tile(palpix, T, palsize);
+    if (bad >= 0) {
+        set_error("smooth: tile " + std::to_string(bad) + " has a palette index >= the palette size " +
+                  std::to_string(palsize));
         return -1;
     }
     const long n = (long)F * Q;
@@ -317,8 +332,9 @@ int smooth_keyframe_host(int F, int Q, int32_t *tile, int32_t *tmpidx, int32_t *
     int32_t *d_tile = s.inout(tile, n), *d_tmp = s.inout(tmpidx, n), *d_pal = s.inout(pal, n);
     uint8_t *d_hm = s.inout(hm, n), *d_vm = s.inout(vm, n), *d_sm = s.inout(smoothed, n);
     const uint8_t *d_pp = s.in(palpix, (size_t)T * 64);
-    const int32_t *d_pals = s.in(palettes, (size_t)P * 16);
-    if (!s.ok() || smooth_keyframe_dev(F, Q, d_tile, d_tmp, d_pal, d_hm, d_vm, d_sm, d_pp, d_pals, strength, s.stream()))
+    const int32_t *d_pals = s.in(palettes, (size_t)P * palsize);
+    if (!s.ok() ||
+        smooth_keyframe_dev(F, Q, d_tile, d_tmp, d_pal, d_hm, d_vm, d_sm, d_pp, d_pals, palsize, strength, s.stream()))
         return -1;
     return s.finish();
 }

@@ -4,7 +4,7 @@ MakeUnique -> GlobalTiling -> FrameTiling -> Reindex -> Smooth), as host state +
 `Encoder` holds what TMainForm keeps in FTiles / FFrames / FKeyFrames for these steps, as flat arrays:
   tiles    palpix [T][64] u8, thm/tvm (TTile.HMirror/VMirror), active, use_count, dith_pal
   tilemaps tile/pal/hm/vm [F][Q] (TFrame.TileMap), sm_* the SmoothedTileMap copies
-  keyframes kf_start [KF+1], palettes [KF][P][16], centroids [KF][P][192]
+  keyframes kf_start [KF+1], palettes [KF][P][palsize], centroids [KF][P][192]
 Each method is the reference procedure of the same name (file:line in its docstring); the heavy parts
 (K-Modes, the k=8 preselection, candidate descriptors, the FrameTiling search, Smooth) run on the GPU
 through the C ABI, the rest is the reference's host bookkeeping -- MakeTilesUnique too unless the encoder is made
@@ -24,14 +24,14 @@ from .synth import Video, video_from_frames
 
 
 def load_and_dither(frames, tm_w: int, tm_h: int, palettes_fn=None, n_palettes: int = 8, gamma: int = -1,
-                    use_wavelets: bool = True, use_dl3: bool = True, pal_var: float = 0.95) -> Video:
+                    use_wavelets: bool = True, use_dl3: bool = True, pal_var: float = 0.95, palsize: int = 16) -> Video:
     """The Load and Dither steps in front of the chain on the GPU (btnLoadClick main.pas:1099-1146, btnDitherClick
     main.pas:858-914): keyframes from the inter-frame correlations, then the keyframe palettes -- PrepareDitherTiles
     (LAB descriptors + k-means -> DitheringPalIndex, PaletteCentroids), QuantizePalette (DLv3), FinishQuantizePalette
     (tiler_amd.palette); use_dl3=False takes QuantizePalette's value-at-risk path with PalVAR = pal_var (chkUseDL3
     unticked, sePalVAR / 100) -- and every tile dithered with its palette (FinishDitherTiles).  palettes_fn(k,
-    frames_of_keyframe) -> [P][16], when given, replaces the palette generation (with the stand-in palette choice
-    of synth.video_from_frames)."""
+    frames_of_keyframe) -> [P][palsize], when given, replaces the palette generation (with the stand-in palette
+    choice of synth.video_from_frames).  palsize: the tile palette size (cbxPalSize: 2, 4, 8, 16, 32 or 64)."""
     from .dither import dither_tiles
     from .keyframes import detect_keyframes
     from .palette import generate_palettes
@@ -41,10 +41,10 @@ def load_and_dither(frames, tm_w: int, tm_h: int, palettes_fn=None, n_palettes: 
     if palettes_fn is not None:
         pals = np.stack([np.asarray(palettes_fn(k, frames[kf_start[k]:kf_start[k + 1]]), np.int32)
                          for k in range(kf_start.size - 1)])
-        return video_from_frames(frames, kf_of, pals, dither_tiles)
-    pals, cents, dith, _ = generate_palettes(frames, kf_start, n_palettes, gamma=gamma, use_wavelets=use_wavelets,
-                                             use_dl3=use_dl3, pal_var=pal_var)
-    return video_from_dither(frames, kf_start, pals, cents, dith, dither_tiles)
+        return video_from_frames(frames, kf_of, pals, dither_tiles, palsize)
+    pals, cents, dith, _ = generate_palettes(frames, kf_start, n_palettes, palsize, gamma=gamma,
+                                             use_wavelets=use_wavelets, use_dl3=use_dl3, pal_var=pal_var)
+    return video_from_dither(frames, kf_start, pals, cents, dith, dither_tiles, palsize)
 
 
 class Encoder:
@@ -52,10 +52,13 @@ class Encoder:
     None = all).  The tileset (palpix, flags, Active, UseCount) is always the whole clip's.  Tilemap arrays are
     [len(frames)][Q]: row r is frame frames[r]."""
 
-    def __init__(self, v: Video, palsize: int = 16, frames=None, gpu_unique: bool = False,
+    def __init__(self, v: Video, palsize: int | None = None, frames=None, gpu_unique: bool = False,
                  gpu_reindex: bool = False):
         F, Q = v.frames, v.tiles_per_frame
-        self.palsize = palsize
+        vsize = int(np.asarray(v.palettes).shape[-1])  # the palette size is the palettes' last dimension
+        if palsize is not None and int(palsize) != vsize:
+            raise ValueError(f"palsize {palsize} given, but the video's palettes have {vsize} entries")
+        self.palsize = vsize
         self.gpu_unique = bool(gpu_unique)  # MakeTilesUnique on the GPU (tiler_make_tiles_unique)
         # UseCount, ReindexTiles and every TileMap remap on the GPU (tiler_tile_use_count, tiler_reindex_tiles,
         # tiler_gather_tiles, tiler_remap_items); the arrays stay numpy, as with gpu_unique
@@ -390,7 +393,7 @@ class DistributedEncoder(Encoder):
     do_reload_tiling is inherited: every rank matches the whole, replicated tile list against the saved tileset and
     gets the same answer; sharding the match across ranks is out of scope."""
 
-    def __init__(self, v: Video, palsize: int = 16, device: int | None = None, save_rank: int = 0,
+    def __init__(self, v: Video, palsize: int | None = None, device: int | None = None, save_rank: int = 0,
                  gpu_unique: bool = False, gpu_reindex: bool = False):
         import os
 

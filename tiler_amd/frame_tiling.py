@@ -16,7 +16,7 @@ import numpy as np
 
 from ._lib import check, load
 from .ann import KDTree
-from .psyv import FROM_PAL, WAVELETS, psyv_batch
+from .psyv import FROM_PAL, WAVELETS, palette_rows, psyv_batch
 from .synth import FTDataset, ft_dataset_from_used, hflip, vflip
 
 FT_FAST, FT_MEDIUM, FT_SLOW = 0, 1, 2
@@ -137,7 +137,7 @@ class KeyframeTiler:
 def prepare_frame_tiling(tiles, thm, tvm, palettes, gds: GlobalDS, item_pal, item_tile, quality: int = FT_MEDIUM,
                          palette_centroids=None, use_wavelets: bool = True, gamma: int = -1) -> KeyframeTiler:
     """PrepareFrameTiling main.pas:3791-3967: used table -> DoPsyV dataset -> index."""
-    P = np.asarray(palettes).reshape(-1, 16).shape[0]
+    P = palette_rows(palettes).shape[0]
     corrs, highest = (None, 0.0)
     if quality == FT_MEDIUM:
         corrs, highest = palette_corr(palette_centroids)
@@ -155,9 +155,10 @@ def near_palettes(palette_centroids, paltol: float = CFT_PALETTE_TOL) -> np.ndar
 def prepare_frame_tiling_dev(gds: GlobalDS, d_item_tile: int, d_item_pal: int, n_items: int, d_palpix: int,
                              d_thm: int, d_tvm: int, n_tiles: int, d_palettes: int, n_palettes: int,
                              quality: int = FT_MEDIUM, near: np.ndarray | None = None, use_wavelets: bool = True,
-                             gamma: int = -1, stream: int = 0):
+                             gamma: int = -1, stream: int = 0, palsize: int = 16):
     """PrepareFrameTiling main.pas:3791-3967 on the device (tiler_prepare_frame_tiling_dev): the keyframe's
     tilemap items (HBM int32 pointers) -> UseOne's k = 8 preselection -> used -> DoPsyV dataset -> search handle.
+    d_palettes is [n_palettes][palsize].
     Returns (KDTree over the keyframe's candidates with its maps set, {"items", "candidates"})."""
     from ._lib import PrepareInfo
     lib = load()
@@ -168,11 +169,11 @@ def prepare_frame_tiling_dev(gds: GlobalDS, d_item_tile: int, d_item_pal: int, n
             raise ValueError("Medium quality needs the near-palette table (near_palettes)")
         nr = np.ascontiguousarray(near, np.uint8)
     vp = ctypes.c_void_p
-    h = lib.tiler_prepare_frame_tiling_dev(gds.kdt.handle, vp(d_item_tile), vp(d_item_pal), int(n_items),
-                                           vp(d_palpix), vp(d_thm), vp(d_tvm), int(n_tiles), vp(d_palettes),
-                                           int(n_palettes), int(quality),
-                                           nr.ctypes.data_as(vp) if nr is not None else None, int(use_wavelets),
-                                           int(gamma), vp(stream), ctypes.byref(info))
+    h = lib.tiler_prepare_frame_tiling_ps_dev(gds.kdt.handle, vp(d_item_tile), vp(d_item_pal), int(n_items),
+                                              vp(d_palpix), vp(d_thm), vp(d_tvm), int(n_tiles), vp(d_palettes),
+                                              int(n_palettes), int(palsize), int(quality),
+                                              nr.ctypes.data_as(vp) if nr is not None else None, int(use_wavelets),
+                                              int(gamma), vp(stream), ctypes.byref(info))
     if not h:
-        check(-1, "tiler_prepare_frame_tiling_dev")
+        check(-1, "tiler_prepare_frame_tiling_ps_dev")
     return KDTree.adopt(h, info.candidates, 192), {"items": int(info.items), "candidates": int(info.candidates)}

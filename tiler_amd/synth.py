@@ -200,7 +200,7 @@ class Video:
     the lowest total error (NOT the reference's ditherer) and canonicalised like PrepareTileMirrors."""
     frame_rgb: np.ndarray      # [F][Q][64] int32
     kf_start: np.ndarray       # [KF+1]
-    palettes: np.ndarray       # [KF][P][16] int32
+    palettes: np.ndarray       # [KF][P][palsize] int32
     centroids: np.ndarray      # [KF][P][192] float64
     palpix: np.ndarray         # [F*Q][64] u8 (canonical orientation)
     thm: np.ndarray            # [F*Q] u8
@@ -217,14 +217,16 @@ class Video:
 
 
 def palette_centroids(pals: np.ndarray) -> np.ndarray:
-    """Deterministic 192-d palette centroids (the reference takes yakmo's, main.pas:2477-2479): the 16
-    colours sorted by luma, RGB/255, repeated 4x.  Close palettes get close centroids."""
-    pals = np.asarray(pals, np.int64).reshape(-1, 16)
+    """Deterministic 192-d palette centroids (the reference takes yakmo's, main.pas:2477-2479): the palette's
+    colours (pals [P][palsize]; 16 for a flat array) sorted by luma, RGB/255, repeated to 192 values (16 colours:
+    4x).  Close palettes get close centroids."""
+    pals = np.asarray(pals, np.int64)
+    pals = pals.reshape(-1, pals.shape[-1] if pals.ndim >= 2 else 16)
     rgb = np.stack([pals & 255, (pals >> 8) & 255, (pals >> 16) & 255], -1).astype(np.float64) / 255.0
     luma = rgb @ np.array([0.2126, 0.7152, 0.0722])
     order = np.argsort(luma, axis=1, kind="stable")
-    srt = np.take_along_axis(rgb, order[..., None], 1).reshape(pals.shape[0], 48)
-    return np.tile(srt, (1, 4))
+    srt = np.take_along_axis(rgb, order[..., None], 1).reshape(pals.shape[0], 3 * pals.shape[1])
+    return np.tile(srt, (1, -(-192 // srt.shape[1])))[:, :192]
 
 
 def video(seed: int, width: int, height: int, kf_frames=(3, 3), n_palettes: int = 8, change: float = 0.3) -> Video:
@@ -268,11 +270,17 @@ def choose_palettes(frame_rgb: np.ndarray, pals: np.ndarray, kf_of: np.ndarray):
     return dith, palpix
 
 
-def video_from_frames(frames: np.ndarray, kf_of_frame, pals: np.ndarray, ditherer) -> Video:
+def _check_palsize(pals: np.ndarray, palsize) -> None:
+    if palsize is not None and pals.shape[-1] != palsize:
+        raise ValueError(f"palettes have {pals.shape[-1]} entries, palsize says {palsize}")
+
+
+def video_from_frames(frames: np.ndarray, kf_of_frame, pals: np.ndarray, ditherer, palsize: int | None = None) -> Video:
     """Load -> Dither without synthetic shortcuts for the parts that are built: keyframes from the Load step's
     split (kf_of_frame), every tile dithered by `ditherer(rgb, pal_of, palettes) -> (palpix, hm, vm)` (DitherTile
     Thomas Knoll + PrepareTileMirrors: tiler_amd.dither.dither_tiles, or the oracle's restatement) with the
-    keyframe palettes pals[KF][P][16] and the stand-in DitheringPalIndex choice above."""
+    keyframe palettes pals[KF][P][palsize] and the stand-in DitheringPalIndex choice above."""
+    _check_palsize(pals, palsize)
     frames = np.ascontiguousarray(frames, np.int32)
     F, q = frames.shape[:2]
     kf_of = np.asarray(kf_of_frame, np.int64)
@@ -286,10 +294,11 @@ def video_from_frames(frames: np.ndarray, kf_of_frame, pals: np.ndarray, dithere
 
 
 def video_from_dither(frames: np.ndarray, kf_start, pals: np.ndarray, centroids: np.ndarray, dith: np.ndarray,
-                      ditherer) -> Video:
-    """Load -> Dither with generated palettes: keyframe palettes pals [KF][P][16], PaletteCentroids [KF][P][192] and
-    every tile's DitheringPalIndex dith [F*Q] (tiler_amd.palette.generate_palettes or the oracle's), every tile
+                      ditherer, palsize: int | None = None) -> Video:
+    """Load -> Dither with generated palettes: keyframe palettes pals [KF][P][palsize], PaletteCentroids [KF][P][192]
+    and every tile's DitheringPalIndex dith [F*Q] (tiler_amd.palette.generate_palettes or the oracle's), every tile
     dithered by `ditherer(rgb, pal_of, palettes)` (FinishDitherTiles main.pas:2482-2544)."""
+    _check_palsize(np.asarray(pals), palsize)
     frames = np.ascontiguousarray(frames, np.int32)
     F, q = frames.shape[:2]
     kf_start = np.asarray(kf_start, np.int64)

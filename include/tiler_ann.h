@@ -533,6 +533,42 @@ int tiler_finish_quantize_order(int n_palettes, const int32_t *use_count, int32_
  * 0 ok, -1 error (tiler_last_error). */
 int tiler_lzma_encode(const uint8_t *src, size_t n, int lc, int lp, int pb, uint32_t dict_size, int eos,
                       uint8_t *dst, size_t cap, size_t *out_len);
+/* ---- LZMA match tables: the match search of tiler_lzma_encode ahead of its parse, on the host or on the GPU ----
+ * A match table holds, for every position p of a buffer, what the encoder's match finder answers there, as
+ * len | dist << 9 in one uint32: len 0 (no match; the whole entry is 0) or 2..273, dist = the back distance - 1.
+ * The finder's rule (hash chains of 2^18 buckets, depth 24, nice length 128): the candidates of p are the positions
+ * q < p with q + 3 <= n whose three bytes hash to p's bucket (collisions included), nearest first; at most 24 are
+ * looked at (one whose bytes differ at once still counts), the walk stops at the first with p - q > dict; with
+ * lim = min(273, n - p) a candidate replaces the best only if strictly longer, and the walk ends after one of length
+ * >= 128 or == lim; a result below 2, and every p with p + 3 > n, is 0.  That answer depends on the buffer and p
+ * alone, so a parse that reads it from a table writes the stream of tiler_lzma_encode, byte for byte.  The packing
+ * needs dict <= 2^21 (the GTM writer's dictionary): these entry points refuse a larger one.
+ *
+ * tiler_lzma_match_table: the table of src[0..n) into table[n] with the encoder's own finder (host code, no GPU). */
+int tiler_lzma_match_table(const uint8_t *src, size_t n, uint32_t dict_size, uint32_t *table);
+/* tiler_lzma_encode with the finder answered from table[n] (no hash chains are built).  Every entry the parse reads
+ * is checked before it is acted on -- len <= min(273, n - p), dist + 1 <= p, dist < dict_size, and the len bytes
+ * equal -- else -1, the message names the position: a wrong table never yields a stream that decodes to other bytes,
+ * nor a read outside src.  table == NULL: tiler_lzma_encode. */
+int tiler_lzma_encode_table(const uint8_t *src, size_t n, int lc, int lp, int pb, uint32_t dict_size, int eos,
+                            const uint32_t *table, uint8_t *dst, size_t cap, size_t *out_len);
+/* The tables of S streams that lie back to back in HBM (as tiler_gtm_commands_dev leaves them): stream k is
+ * d_src[raw_off[k] .. raw_off[k + 1]) (raw_off: HOST, [S + 1], from 0, non-decreasing; d_src at any alignment), its
+ * table d_table[raw_off[k] ..] (HBM, 4-byte aligned).  Streams never match across their borders.  One hash pass, one
+ * stable radix sort of (stream, hash) with the position as value, and a kernel that compares a position with its up
+ * to 24 predecessors in the sorted order.  Scratch is one stream-ordered block of at most 1 GiB (16 bytes per raw
+ * byte and the sort's own), so whole streams are taken in batches of at most 2^26 bytes.  A stream longer than that
+ * (or than 2^31 - 1 bytes) is left to the host finder: its part of d_table is not written.  Queued on `stream`
+ * (asynchronous).  Returns the number of streams left without a table (0: none), or -1. */
+int tiler_lzma_match_table_dev(const uint8_t *d_src, const int64_t *raw_off, int S, uint32_t dict_size,
+                               uint32_t *d_table, void *stream);
+/* One stream from host arrays (staged to HBM and back); a stream above the batch limit is answered by
+ * tiler_lzma_match_table instead, so table[n] is always complete.  0 / -1. */
+int tiler_lzma_match_table_gpu(const uint8_t *src, size_t n, uint32_t dict_size, uint32_t *table);
+/* Test hook (process-wide): the scratch budget of tiler_lzma_match_table_dev in bytes (a batch holds at most
+ * budget_bytes / 16 raw bytes; at least 1 KiB), 0 = the default, 1 GiB.  Tables are identical for every budget that
+ * holds the longest stream.  Returns the previous budget, or -1. */
+int64_t tiler_debug_lzma_match(int64_t budget_bytes);
 /* The inverse (host code): one LZMA-alone stream at src[0..n) -> dst[0..cap); any valid lc / lp / pb, the end-marker
  * and the known-size form.  0: done, *out_len = the decoded bytes, *consumed (optional) = the compressed bytes the
  * stream took, header included, so concatenated streams can be walked.  TILER_LZMA_GROW: cap is too small -- *out_len
@@ -657,6 +693,11 @@ int tiler_gtm_assemble(const uint8_t *comps, const size_t *comp_len, const int32
 int tiler_gtm_write_dev(const tiler_gtm_source_t *src, int threads, uint8_t *dst, size_t cap, size_t *out_len,
                         void *stream);
 int tiler_gtm_write(const tiler_gtm_source_t *src, int threads, uint8_t *dst, size_t cap, size_t *out_len);
+/* Process-wide switch (atomic), default 0.  On: tiler_gtm_streams(_dev) and tiler_gtm_write(_dev) queue
+ * tiler_lzma_match_table_dev behind the command kernels, copy each stream's table to the host with its bytes and
+ * compress with tiler_lzma_encode_table; a stream the table call leaves out is compressed as with the switch off.
+ * The files are the same, byte for byte.  Returns the previous value. */
+int tiler_gtm_set_gpu_matches(int on);
 
 #ifdef __cplusplus
 }

@@ -195,6 +195,12 @@ _SIGS = {
     "tiler_debug_psyv_lane_items": (c_int, [ctypes.c_int64]),
     "tiler_lzma_encode": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_uint32, c_int, c_void_p, c_size_t,
                                   c_void_p]),
+    "tiler_lzma_match_table": (c_int, [c_void_p, c_size_t, c_uint32, c_void_p]),
+    "tiler_lzma_encode_table": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_uint32, c_int, c_void_p, c_void_p,
+                                        c_size_t, c_void_p]),
+    "tiler_lzma_match_table_dev": (c_int, [c_void_p, c_void_p, c_int, c_uint32, c_void_p, c_void_p]),
+    "tiler_lzma_match_table_gpu": (c_int, [c_void_p, c_size_t, c_uint32, c_void_p]),
+    "tiler_debug_lzma_match": (ctypes.c_int64, [ctypes.c_int64]),
     "tiler_lzma_decode": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, P(c_size_t), P(c_size_t)]),
     "tiler_gtm_open": (c_void_p, [c_void_p, c_size_t, c_int, c_size_t]),
     "tiler_gtm_close": (c_int, [c_void_p]),
@@ -216,6 +222,7 @@ _SIGS = {
                                    P(c_size_t)]),
     "tiler_gtm_write_dev": (c_int, [P(GtmSource), c_int, c_void_p, c_size_t, P(c_size_t), c_void_p]),
     "tiler_gtm_write": (c_int, [P(GtmSource), c_int, c_void_p, c_size_t, P(c_size_t)]),
+    "tiler_gtm_set_gpu_matches": (c_int, [c_int]),
 }
 
 _lib = None

@@ -27,6 +27,7 @@
 #include "kmeans.hpp"
 #include "detmath.hpp"
 #include "keyframes.hpp"
+#include "lzma_match.hpp"
 #include "kmodes.hpp"
 #include "nn_search.hpp"
 #include "orbit.hpp"
@@ -1887,5 +1888,22 @@ int tiler_gtm_write(const tiler_gtm_source_t *src, int threads, uint8_t *dst, si
     if (!ensure_init()) return -1;
     return gtm_pack_host(src, threads, true, dst, cap, nullptr, out_len);
 }
+
+int tiler_gtm_set_gpu_matches(int on) { return gtm_set_gpu_matches(on); }
+
+// ---- LZMA match tables on the device (lzma_match.hip); the host forms are in lzma_alone.cpp
+int tiler_lzma_match_table_dev(const uint8_t *d_src, const int64_t *raw_off, int S, uint32_t dict_size,
+                               uint32_t *d_table, void *stream) {
+    if (!ensure_init()) return -1;
+    DevScope ds(ptr_device(d_table));
+    return lzma_match_table_dev(d_src, raw_off, S, dict_size, d_table, stream, nullptr);
+}
+
+int tiler_lzma_match_table_gpu(const uint8_t *src, size_t n, uint32_t dict_size, uint32_t *table) {
+    if (!ensure_init()) return -1;
+    return lzma_match_table_host(src, n, dict_size, table);
+}
+
+int64_t tiler_debug_lzma_match(int64_t budget_bytes) { return lzma_match_debug(budget_bytes); }
 
 }  // extern "C"

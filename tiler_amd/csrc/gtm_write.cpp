@@ -11,6 +11,7 @@
 #include <sched.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstring>
 
@@ -25,15 +26,20 @@ int usable_cpus() {
     return (int)std::max(1u, std::thread::hardware_concurrency());
 }
 
-bool compress(const std::vector<uint8_t> &raw, std::vector<uint8_t> &out, std::string &msg) {
+std::atomic<int> g_gpu_matches{0};
+
+// with a table of raw's size the finder's answers are read from it (the same bytes); else the host finder
+bool compress(const std::vector<uint8_t> &raw, const std::vector<uint32_t> &table, std::vector<uint8_t> &out,
+              std::string &msg) {
     const uint8_t none = 0;
     const uint8_t *src = raw.empty() ? &none : raw.data();
+    const uint32_t *tab = !raw.empty() && table.size() == raw.size() ? table.data() : nullptr;
     out.resize(raw.size() + raw.size() / 32 + 4096);  // LZMA expands incompressible data by less than 2 %
     size_t n = 0;
-    int rc = tiler_lzma_encode(src, raw.size(), 8, 0, 2, 1u << 21, 1, out.data(), out.size(), &n);
+    int rc = tiler_lzma_encode_table(src, raw.size(), 8, 0, 2, 1u << 21, 1, tab, out.data(), out.size(), &n);
     if (rc != 0 && n > out.size()) {
         out.resize(n);
-        rc = tiler_lzma_encode(src, raw.size(), 8, 0, 2, 1u << 21, 1, out.data(), out.size(), &n);
+        rc = tiler_lzma_encode_table(src, raw.size(), 8, 0, 2, 1u << 21, 1, tab, out.data(), out.size(), &n);
     }
     if (rc != 0) {
         msg = last_error();
@@ -57,6 +63,9 @@ bool as_u32(double r, uint32_t &out) {
 
 }  // namespace
 
+int gtm_set_gpu_matches(int on) { return g_gpu_matches.exchange(on ? 1 : 0); }
+bool gtm_gpu_matches() { return g_gpu_matches.load() != 0; }
+
 double fpc_round(double x) {
     const double lo = std::floor(x), d = x - lo;  // exact
     if (d > 0.5) return lo + 1.0;
@@ -65,7 +74,7 @@ double fpc_round(double x) {
 }
 
 GtmPacker::GtmPacker(int keyframes, int threads)
-    : raw_((size_t)std::max(0, keyframes)), comp_(raw_.size()), msg_(raw_.size()) {
+    : raw_((size_t)std::max(0, keyframes)), comp_(raw_.size()), table_(raw_.size()), msg_(raw_.size()) {
     const int want = threads > 0 ? threads : std::min(16, usable_cpus());
     const int n = std::min(want, (int)raw_.size());
     for (int t = 0; t < n; t++) pool_.emplace_back([this] { work(); });
@@ -99,7 +108,7 @@ void GtmPacker::work() {
             k = queue_.front();
             queue_.pop_front();
         }
-        compress(raw_[(size_t)k], comp_[(size_t)k], msg_[(size_t)k]);
+        compress(raw_[(size_t)k], table_[(size_t)k], comp_[(size_t)k], msg_[(size_t)k]);
         {
             std::lock_guard<std::mutex> lk(mu_);
             done_++;

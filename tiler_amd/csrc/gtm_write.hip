@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "gtm_write.hpp"
+#include "lzma_match.hpp"
 #include "stage.hpp"
 
 namespace tiler {
@@ -447,11 +448,25 @@ int gtm_pack_dev(const tiler_gtm_source_t *src, int threads, bool whole_file, ui
         uint8_t *d_raw = nullptr;
         TILER_HIP_CHECK(hipMallocAsync((void **)&d_raw, std::max<size_t>((size_t)raw_off[(size_t)KF], 256), st));
         int rc = gw_emit(src, sc, d_raw, st);
-        // a keyframe's stream to the host, then to the compressors while the next one is copied
+        // tiler_gtm_set_gpu_matches: every stream's match table behind the command kernels (lzma_match.hip)
+        uint32_t *d_table = nullptr;
+        std::vector<uint8_t> has_table;
+        if (rc == 0 && gtm_gpu_matches() && raw_off[(size_t)KF] > 0) {
+            hipError_t e = hipMallocAsync((void **)&d_table, (size_t)raw_off[(size_t)KF] * 4, st);
+            if (e != hipSuccess) rc = gw_fail(std::string("the match tables: ") + hipGetErrorString(e));
+            if (rc == 0 && lzma_match_table_dev(d_raw, raw_off.data(), KF, 1u << 21, d_table, st, &has_table) < 0) rc = -1;
+        }
+        // a keyframe's stream (and its table) to the host, then to the compressors while the next one is copied
         for (int k = 0; k < KF && rc == 0; k++) {
             std::vector<uint8_t> &r = pk.raw(k);
             r.resize((size_t)(raw_off[(size_t)k + 1] - raw_off[(size_t)k]));
             hipError_t e = hipMemcpyAsync(r.data(), d_raw + raw_off[(size_t)k], r.size(), hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess && d_table && has_table[(size_t)k] && !r.empty()) {
+                KTimer tm("gtm_table_copy", st);
+                std::vector<uint32_t> &t = pk.table(k);
+                t.resize(r.size());
+                e = hipMemcpyAsync(t.data(), d_table + raw_off[(size_t)k], t.size() * 4, hipMemcpyDeviceToHost, st);
+            }
             if (e == hipSuccess) e = hipStreamSynchronize(st);
             if (e != hipSuccess) {
                 rc = gw_fail(std::string("copying a stream to the host: ") + hipGetErrorString(e));
@@ -459,6 +474,7 @@ int gtm_pack_dev(const tiler_gtm_source_t *src, int threads, bool whole_file, ui
             }
             pk.ready(k);
         }
+        if (d_table) (void)hipFreeAsync(d_table, st);
         (void)hipFreeAsync(d_raw, st);
         if (rc) return -1;
     }

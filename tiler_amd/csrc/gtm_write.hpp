@@ -27,6 +27,8 @@ class GtmPacker {
     GtmPacker(const GtmPacker &) = delete;
     GtmPacker &operator=(const GtmPacker &) = delete;
     std::vector<uint8_t> &raw(int k) { return raw_[(size_t)k]; }
+    // stream k's match table (tiler_lzma_encode_table), one entry per byte of raw(k); left empty: the host finder
+    std::vector<uint32_t> &table(int k) { return table_[(size_t)k]; }
     void ready(int k);
     // waits until every keyframe is compressed; false with set_error() when one failed (or was never made ready)
     bool finish();
@@ -36,6 +38,7 @@ class GtmPacker {
   private:
     void work();
     std::vector<std::vector<uint8_t>> raw_, comp_;
+    std::vector<std::vector<uint32_t>> table_;
     std::vector<std::string> msg_;
     std::mutex mu_;
     std::condition_variable cv_, done_cv_;
@@ -44,6 +47,10 @@ class GtmPacker {
     bool stop_ = false;
     std::vector<std::thread> pool_;
 };
+
+// tiler_gtm_set_gpu_matches: the process-wide switch (atomic), read by gtm_pack_dev
+int gtm_set_gpu_matches(int on);
+bool gtm_gpu_matches();
 
 // FPC Round: to nearest, ties to even, whatever the floating-point rounding mode is
 double fpc_round(double x);

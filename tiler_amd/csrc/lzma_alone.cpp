@@ -12,9 +12,13 @@
 // + direct bits + 4 align bits, rep0..rep3 and short rep, end marker = distance 0xFFFFFFFF.  Parsing is
 // greedy with one step of lazy evaluation over hash chains (3-byte hash); any valid parse decodes to the
 // same bytes, so the output differs from lzma.exe's bytes but not in what a decoder returns.
+// The parse is written once over two finders: the hash chains (tiler_lzma_encode), or a match table computed ahead
+// of it, on the host (tiler_lzma_match_table) or on the GPU (lzma_match.hip), whose entries tiler_lzma_encode_table
+// checks as it reads them.  Both write the same stream.
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "host_error.hpp"
@@ -246,6 +250,12 @@ struct Encoder {
     }
 };
 
+uint32_t match_len(const uint8_t *buf, size_t a, size_t b, uint32_t lim) {
+    uint32_t l = 0;
+    while (l < lim && buf[a + l] == buf[b + l]) l++;
+    return l;
+}
+
 // hash-chain match finder over the whole input (the window is the dictionary)
 struct MatchFinder {
     const uint8_t *buf;
@@ -268,13 +278,9 @@ struct MatchFinder {
         prev[p] = head[h];
         head[h] = (int64_t)p;
     }
-    uint32_t match_len(size_t a, size_t b, uint32_t lim) const {
-        uint32_t l = 0;
-        while (l < lim && buf[a + l] == buf[b + l]) l++;
-        return l;
-    }
+    bool failed() const { return false; }
     // longest match at p (not yet inserted): returns len (0 if < kMinLen) and back distance - 1
-    uint32_t best(size_t p, uint32_t &dist) const {
+    uint32_t best(size_t p, uint32_t &dist) {
         if (p + 3 > n) return 0;
         const uint32_t lim = (uint32_t)std::min<size_t>(kMaxLen, n - p);
         uint32_t bl = 0;
@@ -283,7 +289,7 @@ struct MatchFinder {
             const size_t back = p - (size_t)c;
             if (back > dict) break;
             if (buf[(size_t)c + bl] != buf[p + bl]) continue;
-            const uint32_t l = match_len((size_t)c, p, lim);
+            const uint32_t l = match_len(buf, (size_t)c, p, lim);
             if (l > bl) {
                 bl = l;
                 dist = (uint32_t)(back - 1);
@@ -294,24 +300,45 @@ struct MatchFinder {
     }
 };
 
-}  // namespace
+// A match table (include/tiler_ann.h): best(p) of every position, computed ahead of the parse.  best() depends on the
+// buffer and p alone -- every branch of the parse has inserted all positions below p by the time it asks for p -- so
+// the parse that reads the table makes the decisions of the one that walks the chains.  An entry is checked before it
+// is acted on: a wrong table ends the call, it never yields a stream that decodes to other bytes.
+constexpr uint32_t kTableLenBits = 9, kTableMaxDict = 1u << 21;
 
-extern "C" int tiler_lzma_encode(const uint8_t *src, size_t n, int lc, int lp, int pb, uint32_t dict_size, int eos,
-                                 uint8_t *dst, size_t cap, size_t *out_len) {
-    if ((!src && n) || !out_len || lc < 0 || lc > 8 || lp < 0 || lp > 4 || pb < 0 || pb > 4 || dict_size < 4096) {
-        tiler::set_error("tiler_lzma_encode: bad arguments (lc 0..8, lp 0..4, pb 0..4, dict >= 4096)");
-        return -1;
+struct TableFinder {
+    const uint8_t *buf;
+    size_t n;
+    uint32_t dict;
+    const uint32_t *table;
+    bool bad = false;
+    size_t bad_pos = 0;
+
+    TableFinder(const uint8_t *b, size_t nn, uint32_t d, const uint32_t *t) : buf(b), n(nn), dict(d), table(t) {}
+    void insert(size_t) {}
+    bool failed() const { return bad; }
+    uint32_t best(size_t p, uint32_t &dist) {
+        const uint32_t e = table[p];
+        if (e == 0) return 0;
+        const uint32_t len = e & ((1u << kTableLenBits) - 1), d = e >> kTableLenBits;
+        if (len < (uint32_t)kMinLen || len > (uint32_t)kMaxLen || len > n - p || (size_t)d + 1 > p || d >= dict ||
+            std::memcmp(buf + p, buf + p - d - 1, len) != 0) {
+            if (!bad) bad_pos = p;
+            bad = true;
+            return 0;
+        }
+        dist = d;
+        return len;
     }
-    Encoder enc(lc, lp, pb, dict_size);
-    std::vector<uint8_t> hdr(13);
-    hdr[0] = (uint8_t)((pb * 5 + lp) * 9 + lc);
-    for (int i = 0; i < 4; i++) hdr[1 + i] = (uint8_t)(dict_size >> (8 * i));
-    for (int i = 0; i < 8; i++) hdr[5 + i] = eos ? 0xFF : (uint8_t)((uint64_t)n >> (8 * i));
-    MatchFinder mf(src, n, dict_size);
+};
+
+// The parse: greedy with one step of lazy evaluation, over either finder.
+template <class Finder>
+void parse(Encoder &enc, Finder &mf, const uint8_t *src, size_t n) {
     size_t p = 0;
     bool have_next = false;  // the lazy look-ahead of the previous position, reused when it won
     uint32_t next_len = 0, next_dist = 0;
-    while (p < n) {
+    while (p < n && !mf.failed()) {
         const uint32_t lim = (uint32_t)std::min<size_t>(kMaxLen, n - p);
         // rep candidates
         uint32_t rl = 0;
@@ -319,7 +346,7 @@ extern "C" int tiler_lzma_encode(const uint8_t *src, size_t n, int lc, int lp, i
         for (int r = 0; r < 4; r++) {
             const size_t back = (size_t)enc.rep[r] + 1;
             if (back > p) continue;
-            const uint32_t l = mf.match_len(p - back, p, lim);
+            const uint32_t l = match_len(src, p - back, p, lim);
             if (l > rl) {
                 rl = l;
                 ri = r;
@@ -371,16 +398,81 @@ extern "C" int tiler_lzma_encode(const uint8_t *src, size_t n, int lc, int lp, i
             p++;
         }
     }
-    if (eos) enc.end_marker(p);
+}
+
+}  // namespace
+
+namespace {
+
+int encode(const char *who, const uint8_t *src, size_t n, int lc, int lp, int pb, uint32_t dict_size, int eos,
+           const uint32_t *table, uint8_t *dst, size_t cap, size_t *out_len) {
+    const std::string me(who);
+    if ((!src && n) || !out_len || lc < 0 || lc > 8 || lp < 0 || lp > 4 || pb < 0 || pb > 4 || dict_size < 4096) {
+        tiler::set_error(me + ": bad arguments (lc 0..8, lp 0..4, pb 0..4, dict >= 4096)");
+        return -1;
+    }
+    if (table && dict_size > kTableMaxDict) {
+        tiler::set_error(me + ": a match table holds distances below 2^21; dictionary " + std::to_string(dict_size) +
+                         " is larger");
+        return -1;
+    }
+    Encoder enc(lc, lp, pb, dict_size);
+    std::vector<uint8_t> hdr(13);
+    hdr[0] = (uint8_t)((pb * 5 + lp) * 9 + lc);
+    for (int i = 0; i < 4; i++) hdr[1 + i] = (uint8_t)(dict_size >> (8 * i));
+    for (int i = 0; i < 8; i++) hdr[5 + i] = eos ? 0xFF : (uint8_t)((uint64_t)n >> (8 * i));
+    if (table) {
+        TableFinder mf(src, n, dict_size, table);
+        parse(enc, mf, src, n);
+        if (mf.failed()) {
+            tiler::set_error(me + ": the match table is wrong at position " + std::to_string(mf.bad_pos) + " (entry " +
+                             std::to_string(table[mf.bad_pos]) + ": length within the buffer, distance within the " +
+                             "data before it and the dictionary, and equal bytes are required)");
+            return -1;
+        }
+    } else {
+        MatchFinder mf(src, n, dict_size);
+        parse(enc, mf, src, n);
+    }
+    if (eos) enc.end_marker(n);
     enc.rc.flush();
     const size_t total = hdr.size() + enc.rc.out.size();
     *out_len = total;
     if (!dst) return 0;  // size query
     if (cap < total) {
-        tiler::set_error("tiler_lzma_encode: output buffer too small (*out_len holds the size needed)");
+        tiler::set_error(me + ": output buffer too small (*out_len holds the size needed)");
         return -1;
     }
     std::memcpy(dst, hdr.data(), hdr.size());
     std::memcpy(dst + hdr.size(), enc.rc.out.data(), enc.rc.out.size());
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int tiler_lzma_encode(const uint8_t *src, size_t n, int lc, int lp, int pb, uint32_t dict_size, int eos,
+                                 uint8_t *dst, size_t cap, size_t *out_len) {
+    return encode("tiler_lzma_encode", src, n, lc, lp, pb, dict_size, eos, nullptr, dst, cap, out_len);
+}
+
+extern "C" int tiler_lzma_encode_table(const uint8_t *src, size_t n, int lc, int lp, int pb, uint32_t dict_size,
+                                       int eos, const uint32_t *table, uint8_t *dst, size_t cap, size_t *out_len) {
+    return encode(table ? "tiler_lzma_encode_table" : "tiler_lzma_encode", src, n, lc, lp, pb, dict_size, eos, table,
+                  dst, cap, out_len);
+}
+
+extern "C" int tiler_lzma_match_table(const uint8_t *src, size_t n, uint32_t dict_size, uint32_t *table) {
+    if ((!src && n) || (!table && n) || dict_size < 4096 || dict_size > kTableMaxDict) {
+        tiler::set_error("tiler_lzma_match_table: bad arguments (dict in [4096, 2^21]: the table holds distances "
+                         "below 2^21)");
+        return -1;
+    }
+    MatchFinder mf(src, n, dict_size);
+    for (size_t p = 0; p < n; p++) {
+        uint32_t d = 0;
+        const uint32_t l = mf.best(p, d);
+        table[p] = l ? l | d << kTableLenBits : 0;
+        mf.insert(p);
+    }
     return 0;
 }

@@ -251,9 +251,13 @@ class Encoder:
         self.sm = sm
         return sm
 
-    def _keyframe_streams(self, width: int, height: int, fps: float, gpu: bool = False) -> dict:
+    def _keyframe_streams(self, width: int, height: int, fps: float, gpu: bool = False,
+                          gpu_matches: bool = False) -> dict:
         """LZCompress'd command stream of every held keyframe (SaveStream main.pas:4724-4734), compressed
-        concurrently.  gpu: the command words by libANN.so's kernel, LZMA on its thread pool (tiler_gtm_streams)."""
+        concurrently.  gpu: the command words by libANN.so's kernel, LZMA on its thread pool (tiler_gtm_streams);
+        gpu_matches (with gpu): the LZMA match search on the GPU as well."""
+        if gpu_matches and not gpu:
+            raise ValueError("gpu_matches needs gpu=True (the native writer)")
         sm = self.sm
         if sm is None:
             raise RuntimeError("SaveStream needs the SmoothedTileMaps: run do_smooth first")
@@ -266,7 +270,7 @@ class Encoder:
             comps = gtm.keyframe_streams_gpu(self.palpix, self.thm, self.tvm, kf_start, self.palettes[self.kfs],
                                              sm["tile"][r], sm["pal"][r], sm["hm"][r], sm["vm"][r], sm["smoothed"][r],
                                              width=width, height=height, fps=fps, palsize=self.palsize,
-                                             first_keyframe=self.kfs[0] == 0)
+                                             first_keyframe=self.kfs[0] == 0, gpu_matches=gpu_matches)
             return dict(zip(self.kfs, comps))
         raws = []
         for k in self.kfs:
@@ -276,10 +280,11 @@ class Encoder:
                                          height=height, fps=fps, palsize=self.palsize))
         return dict(zip(self.kfs, gtm.compress_streams(raws)))
 
-    def save_stream(self, width: int, height: int, fps: float = 24.0, gpu: bool = False) -> bytes:
+    def save_stream(self, width: int, height: int, fps: float = 24.0, gpu: bool = False,
+                    gpu_matches: bool = False) -> bytes:
         """btnSaveClick -> SaveStream main.pas:4529-4763 (the .gtm bytes; needs do_smooth first).  gpu: the same
-        bytes from the native writer."""
-        comps = self._keyframe_streams(width, height, fps, gpu)
+        bytes from the native writer; gpu_matches (with gpu): its LZMA match search on the GPU, the same bytes."""
+        comps = self._keyframe_streams(width, height, fps, gpu, gpu_matches)
         return gtm.assemble_stream([comps[k] for k in range(self.kf_start.size - 1)], self.kf_start, width, height,
                                    fps)
 
@@ -451,11 +456,14 @@ class DistributedEncoder(Encoder):
                              "collective; pass save_rank's bytes)")
         return super().verify_stream(data, width=width, height=height, fps=fps)
 
-    def save_stream(self, width: int, height: int, fps: float = 24.0, gpu: bool = False) -> bytes | None:
+    def save_stream(self, width: int, height: int, fps: float = 24.0, gpu: bool = False,
+                    gpu_matches: bool = False) -> bytes | None:
         """SaveStream as a collective: every rank writes and compresses its own keyframes' streams (gpu: with the
-        native writer), rank save_rank receives the others' and assembles the file (None on the other ranks)."""
+        native writer; gpu_matches: its LZMA match search on the GPU), rank save_rank receives the others' and
+        assembles the file (None on the other ranks)."""
         from . import dist as tdist
-        comps = tdist.gather_units(self._keyframe_streams(width, height, fps, gpu), self.owner_of, self.save_rank)
+        comps = tdist.gather_units(self._keyframe_streams(width, height, fps, gpu, gpu_matches), self.owner_of,
+                                   self.save_rank)
         if comps is None:
             return None
         return gtm.assemble_stream(comps, self.kf_start, width, height, fps)

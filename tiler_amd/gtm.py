@@ -38,21 +38,61 @@ LZMA_LC, LZMA_LP, LZMA_PB = 8, 0, 2
 LZMA_DICT = 1 << 21             # the reference's lzma.exe streams (docs/demo/*.gtm headers)
 
 
-def lzma_encode(data: bytes, lc: int = LZMA_LC, lp: int = LZMA_LP, pb: int = LZMA_PB, dict_size: int = LZMA_DICT,
-                eos: bool = True) -> bytes:
-    """LZCompress (extern.pas:202-240) on libANN.so: one LZMA-alone stream."""
+def match_table(data: bytes, dict_size: int = LZMA_DICT, gpu: bool = False) -> np.ndarray:
+    """The match table of `data` (include/tiler_ann.h): per position len | dist << 9 as uint32, what the encoder's
+    match finder answers there.  gpu: computed on the device (tiler_lzma_match_table_gpu), else by the finder itself
+    on the host (tiler_lzma_match_table, needs no GPU); the same entries either way.  dict_size <= 2^21."""
     lib = load()
     src = np.frombuffer(data, np.uint8) if len(data) else np.zeros(1, np.uint8)
+    table = np.zeros(len(data), np.uint32)
+    fn, what = ((lib.tiler_lzma_match_table_gpu, "tiler_lzma_match_table_gpu") if gpu else
+                (lib.tiler_lzma_match_table, "tiler_lzma_match_table"))
+    check(fn(src.ctypes.data_as(ctypes.c_void_p), len(data), dict_size, table.ctypes.data_as(ctypes.c_void_p)), what)
+    return table
+
+
+def lzma_encode(data: bytes, lc: int = LZMA_LC, lp: int = LZMA_LP, pb: int = LZMA_PB, dict_size: int = LZMA_DICT,
+                eos: bool = True, matches=None) -> bytes:
+    """LZCompress (extern.pas:202-240) on libANN.so: one LZMA-alone stream.  matches: None -- the encoder searches as
+    it parses; "host" / "gpu" -- the search runs ahead of the parse (match_table) and the parse reads it
+    (tiler_lzma_encode_table); a table (uint32 [len(data)]) is used as given, every entry checked.  The same bytes."""
+    lib = load()
+    src = np.frombuffer(data, np.uint8) if len(data) else np.zeros(1, np.uint8)
+    if isinstance(matches, str):
+        if matches not in ("host", "gpu"):
+            raise ValueError("lzma_encode: matches is None, 'host', 'gpu' or a table")
+        matches = match_table(data, dict_size, gpu=matches == "gpu")
+    if matches is not None:
+        matches = np.ascontiguousarray(matches, np.uint32)
+        if matches.size != len(data):
+            raise ValueError("lzma_encode: the match table has one entry per byte")
+    t = matches.ctypes.data_as(ctypes.c_void_p) if matches is not None and matches.size else None
     n = ctypes.c_size_t(0)
     p = src.ctypes.data_as(ctypes.c_void_p)
     out = np.zeros(len(data) + len(data) // 32 + 4096, np.uint8)  # LZMA expands incompressible data < 2 %
-    if lib.tiler_lzma_encode(p, len(data), lc, lp, pb, dict_size, int(eos), out.ctypes.data_as(ctypes.c_void_p),
-                             out.size, ctypes.byref(n)) != 0:
+    if lib.tiler_lzma_encode_table(p, len(data), lc, lp, pb, dict_size, int(eos), t,
+                                   out.ctypes.data_as(ctypes.c_void_p), out.size, ctypes.byref(n)) != 0:
+        if n.value <= out.size:
+            raise TilerError(f"tiler_lzma_encode failed: {last_error()}")
         out = np.zeros(n.value, np.uint8)
-        check(lib.tiler_lzma_encode(p, len(data), lc, lp, pb, dict_size, int(eos),
-                                    out.ctypes.data_as(ctypes.c_void_p), out.size, ctypes.byref(n)),
+        check(lib.tiler_lzma_encode_table(p, len(data), lc, lp, pb, dict_size, int(eos), t,
+                                          out.ctypes.data_as(ctypes.c_void_p), out.size, ctypes.byref(n)),
               "tiler_lzma_encode")
     return out[:n.value].tobytes()
+
+
+class _GpuMatches:
+    """tiler_gtm_set_gpu_matches for the length of a call (the switch is process-wide), restored afterwards."""
+
+    def __init__(self, on: bool):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.prev = load().tiler_gtm_set_gpu_matches(1) if self.on else None
+
+    def __exit__(self, *exc):
+        if self.on:
+            load().tiler_gtm_set_gpu_matches(self.prev)
 
 
 def fpc_round(x: float) -> int:
@@ -274,31 +314,37 @@ def keyframe_raw_gpu(k: int, palpix, thm, tvm, palettes_k, tile, pal, hm, vm, sm
 
 def keyframe_streams_gpu(palpix, thm, tvm, kf_start, palettes, sm_tile, sm_pal, sm_hm, sm_vm, sm_smoothed, *,
                          width: int, height: int, fps: float, palsize: int = 16, first_keyframe: bool = True,
-                         threads: int | None = None) -> list:
+                         threads: int | None = None, gpu_matches: bool = False) -> list:
     """The LZCompress'd streams of the given keyframes (tiler_gtm_streams; kf_start: rows of the arrays, from 0;
     first_keyframe: the first of them is the file's keyframe 0) -- for a caller that holds only some keyframes and
-    assembles the file later (assemble_stream / tiler_gtm_assemble)."""
+    assembles the file later (assemble_stream / tiler_gtm_assemble).  gpu_matches: the LZMA match search on the GPU
+    too (tiler_gtm_set_gpu_matches for this call); the same bytes."""
     src, keep = gtm_source(palpix, thm, tvm, kf_start, palettes, sm_tile, sm_pal, sm_hm, sm_vm, sm_smoothed,
                            width=width, height=height, fps=fps, palsize=palsize, first_keyframe=first_keyframe)
     lens = np.zeros(src.keyframes, np.uint64)
     raw = _raw_bound(src)
     lib = load()
-    out = _sized_call(lambda d, cap, n: lib.tiler_gtm_streams(ctypes.byref(src), int(threads or 0), d, cap, _vp(lens), n),
-                      "tiler_gtm_streams", raw + raw // 32 + 4096 * src.keyframes)
+    with _GpuMatches(gpu_matches):
+        out = _sized_call(lambda d, cap, n: lib.tiler_gtm_streams(ctypes.byref(src), int(threads or 0), d, cap,
+                                                                  _vp(lens), n),
+                          "tiler_gtm_streams", raw + raw // 32 + 4096 * src.keyframes)
     ends = np.cumsum(lens).astype(np.int64)
     return [out[e - int(n):e].tobytes() for e, n in zip(ends, lens)]
 
 
 def save_stream_gpu(palpix, thm, tvm, kf_start, palettes, sm_tile, sm_pal, sm_hm, sm_vm, sm_smoothed, width: int,
-                    height: int, fps: float, palsize: int = 16, threads: int | None = None) -> bytes:
+                    height: int, fps: float, palsize: int = 16, threads: int | None = None,
+                    gpu_matches: bool = False) -> bytes:
     """save_stream in libANN.so (tiler_gtm_write): the command words on the GPU, LZMA on native threads, the
-    container -- the same file, byte for byte."""
+    container -- the same file, byte for byte.  gpu_matches: the LZMA match search on the GPU too
+    (tiler_gtm_set_gpu_matches for this call); still the same file."""
     src, keep = gtm_source(palpix, thm, tvm, kf_start, palettes, sm_tile, sm_pal, sm_hm, sm_vm, sm_smoothed,
                            width=width, height=height, fps=fps, palsize=palsize)
     raw = _raw_bound(src)
     lib = load()
-    out = _sized_call(lambda d, cap, n: lib.tiler_gtm_write(ctypes.byref(src), int(threads or 0), d, cap, n),
-                      "tiler_gtm_write", raw + raw // 32 + 4096 * src.keyframes + 40 + 28 * src.keyframes)
+    with _GpuMatches(gpu_matches):
+        out = _sized_call(lambda d, cap, n: lib.tiler_gtm_write(ctypes.byref(src), int(threads or 0), d, cap, n),
+                          "tiler_gtm_write", raw + raw // 32 + 4096 * src.keyframes + 40 + 28 * src.keyframes)
     return out.tobytes()
 
 

@@ -14,11 +14,12 @@
  * 32 bits, so CUBE3's colour sums and counts wrap modulo 2^32 exactly as there.  calc_err is the float function of
  * quantizer.c:512-541 (its forward declaration at :357 says ulong; every caller stores the value into a float).
  *
- * Parity: quantizer.c cannot be compiled here without stand-ins (MSVC-only __declspec/__stdcall in quantizer.h,
- * the progress_init/progress_update/progress_end callbacks it calls are defined elsewhere in mtPaint, and the two
- * calc_err declarations conflict), and the reference holds no DLv3 fixture: this restatement is "parity unpinned"
- * against the binary.  TFPList.Sort's tie order (only for distinct colours with equal luma, V, S and H) follows the
- * classic FPC RTL QuickSort (lists.inc); the RTL source is not in the reference -- also unpinned.
+ * Parity: dl3quant is pinned by the reference's own quantizer.c, built with stand-ins by build_ref_dlquant.sh (32-bit
+ * ulong / slong, the MSVC-only keywords and the conflicting calc_err prototype removed, no-op progress callbacks):
+ * its palettes are committed as tests/golden/dl3_ref_kat.npz and compared in tests/test_dl3_ref.py, live too where
+ * the reference tree is present.  The DLL binary itself stays unpinned (MSVC's float code generation).
+ * TFPList.Sort's tie order (only for distinct colours with equal luma, V, S and H) follows the
+ * classic FPC RTL QuickSort (lists.inc); the RTL source is not in the reference -- unpinned.
  */
 #include <math.h>
 #include <pthread.h>

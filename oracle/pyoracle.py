@@ -13,6 +13,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "liboracle.so")
 REF_LIB = os.path.join(HERE, "_ref", "libkmodes_ref.so")
+REF_DLQUANT_LIB = os.path.join(HERE, "_ref", "libdlquant_ref.so")
 
 _o = None
 
@@ -379,6 +380,27 @@ def ref_kmodes_lib():
     r = ctypes.CDLL(REF_LIB)
     r.ref_get_min.restype = ctypes.c_int64
     return r
+
+
+def ref_dlquant_lib():
+    """The reference's own DLv3 quantizer (dlquant/quantizer.c, build_ref_dlquant.sh) if oracle/_ref was built
+    here; else None.  ref_dl3quant takes or_dl3quant's arguments (see ref_dl3quant below)."""
+    if not os.path.exists(REF_DLQUANT_LIB):
+        return None
+    r = ctypes.CDLL(REF_DLQUANT_LIB)
+    r.ref_dl3quant.restype = ctypes.c_int
+    r.ref_dl3quant.argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    return r
+
+
+def ref_dl3quant(ref, pixels, quant_to=16, bpc=7):
+    """dl3quant of the reference build `ref` (ref_dlquant_lib()) over pixels [n][3] u8: palette [quant_to]
+    0x00BBGGRR, unsorted, as dl3quant above returns it."""
+    px = np.ascontiguousarray(pixels, np.uint8).reshape(-1, 3)
+    out = np.zeros(quant_to, np.int32)
+    if ref.ref_dl3quant(_p(px), px.shape[0], quant_to, bpc, _p(out)) != 0:
+        raise RuntimeError("ref_dl3quant failed")
+    return out
 
 
 # ---- palette generation (palette.c): QuantizePalette with DLv3, CompareCMULHS, FinishQuantizePalette ----

@@ -1,8 +1,8 @@
 """CPU tests of palette generation: the oracle's DLv3 restatement (oracle/palette.c) against
 an independent pure-Python restatement of dlquant/quantizer.c:437-663 on small colour sets, RGBToHSV / MulDiv
 known answers, the CompareCMULHS and FinishQuantizePalette orders, and the product's host-side order function.
-quantizer.c itself is not buildable here (MSVC-only declarations, mtPaint progress callbacks, conflicting
-calc_err declarations), so DLv3 parity is unpinned against the reference binary."""
+Both restatements are compared with quantizer.c itself (built with stand-ins by oracle/build_ref_dlquant.sh) in
+tests/test_dl3_ref.py; the DLL binary stays unpinned."""
 import numpy as np
 import pytest
 

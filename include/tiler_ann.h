@@ -164,7 +164,8 @@ int tiler_set_gamma(double g0, double g1); /* gGamma main.pas:586 / 1441-1447; r
  * summed milliseconds and launch count of one kernel family ("psyv", "nn_prep", "nn_shortlist",
  * "nn_rescore", "nn_exact", "smooth", "kmodes", "render", "quality", "reload_match", "unique_insert", "unique_last",
  * "unique_merge", "unique_zero", "ft_dedup": FrameTiling's duplicate-tile passes and scatter, "reindex_count",
- * "reindex_active", "reindex_order", "reindex_gather", "reindex_remap").  Reading synchronises the recorded events. */
+ * "reindex_active", "reindex_order", "reindex_gather", "reindex_remap", "load_frames", "store_frames").  Reading
+ * synchronises the recorded events. */
 int tiler_timing_enable(int on);
 double tiler_timing_get(const char *kernel, int *launches);
 int tiler_timing_reset(void);
@@ -414,6 +415,44 @@ int tiler_interframe_correlation_dev(const int32_t *d_rgb, int F, int tm_w, int 
 /* The shot-transition split (main.pas:1099-1132): kf_of_frame[F] = keyframe index of each frame.
  * tile_map_size = FTileMapSize.  Returns the keyframe count, or -1. */
 int tiler_find_keyframes(const double *corr, int F, int tile_map_size, int32_t *kf_of_frame);
+
+/* ---- Load-step raster ingest (LoadFrame main.pas:3211-3286, ReframeUI main.pas:1931-1938) and its inverse ----
+ * Pictures as a decoder leaves them -> the tile-major frames every other entry point takes, and back.  Decoding
+ * image files stays with the caller; the pictures arrive in memory.
+ * Source: F pictures of src_w x src_h pixels; row j of frame f starts at byte f * frame_stride + j * pitch, with
+ * pitch >= src_w * bpp and frame_stride >= src_h * pitch (any alignment: odd pitches and bases take a byte path at
+ * the ends of a row only).  Pixel formats (alpha / X is dropped, as SwapRB main.pas:561-564 drops it): */
+#define TILER_PIX_RGB24 0  /* bytes R,G,B (ffmpeg -pix_fmt rgb24) */
+#define TILER_PIX_BGR24 1  /* bytes B,G,R */
+#define TILER_PIX_BGRA32 2 /* bytes B,G,R,X: the integer 0x00RRGGBB of a pf32bit ScanLine, which LoadFrame SwapRBs */
+#define TILER_PIX_RGBA32 3 /* bytes R,G,B,X: the integer 0xXXBBGGRR (the GTM player's raster) */
+/* ReframeUI: *tm_w = min(src_w div 8, 240), *tm_h = min(src_h div 8, 135); the picture's top-left tm_w*8 x tm_h*8
+ * pixels are used, the rest ignored.  -1 when src_w or src_h is below 8. */
+int tiler_load_dims(int src_w, int src_h, int *tm_w, int *tm_h);
+/* Pictures in HBM -> d_rgb[F][tm_h*tm_w][64] int32 0x00BBGGRR (16-byte aligned): tile tm_w * (j div 8) + (i div 8),
+ * element (j and 7) * 8 + (i and 7) (main.pas:3252-3258).  Asynchronous on stream.  Every argument is checked
+ * before anything is launched: -1 with tiler_last_error() naming it.  F = 0 does nothing and returns 0. */
+int tiler_load_frames_dev(const uint8_t *d_src, int fmt, int F, int src_w, int src_h, int64_t pitch,
+                          int64_t frame_stride, int32_t *d_rgb, void *stream);
+/* Host arrays.  Staged in chunks of whole frames on a pool stream -- copy in, kernel, copy out -- each chunk at most
+ * 256 MiB of picture plus tile bytes (at least one frame), so a clip of any length needs two device blocks of that
+ * size together.  Only the used rectangle of every picture is copied: row padding is never read. */
+int tiler_load_frames(const uint8_t *src, int fmt, int F, int src_w, int src_h, int64_t pitch, int64_t frame_stride,
+                      int32_t *rgb);
+/* The inverse: rgb[F][tm_h*tm_w][64] (the top byte of a pixel is ignored) -> pictures of tm_w*8 x tm_h*8 pixels in
+ * fmt; X bytes are written 0xFF; the bytes of a row past tm_w * 8 * bpp and between frames are not written. */
+int tiler_store_frames_dev(const int32_t *d_rgb, int F, int tm_w, int tm_h, int fmt, uint8_t *d_dst, int64_t pitch,
+                           int64_t frame_stride, void *stream);
+int tiler_store_frames(const int32_t *rgb, int F, int tm_w, int tm_h, int fmt, uint8_t *dst, int64_t pitch,
+                       int64_t frame_stride);
+/* The Load step in one call: frames tiled into d_rgb, then corr[F-1] and kf_of_frame[F] (host arrays) from them
+ * (tiler_interframe_correlation_dev + tiler_find_keyframes).  Synchronous on stream.  Returns the keyframe count
+ * or -1. */
+int tiler_load_clip_dev(const uint8_t *d_src, int fmt, int F, int src_w, int src_h, int64_t pitch,
+                        int64_t frame_stride, int32_t *d_rgb, double *corr, int32_t *kf_of_frame, void *stream);
+/* Test hook (process-wide): frames per staging chunk of tiler_load_frames / tiler_store_frames; 0 restores the
+ * default (the 256 MiB rule above).  Results are identical for every value.  0 / -1 (frames < 0). */
+int tiler_debug_load_chunk(int64_t frames);
 
 /* ---- Quality readout (Render main.pas:3305-3493, lblCorrel main.pas:3470-3489) ------------------------
  * Render's destination frame from the tilemaps, as Render draws it with dithered, reduced and mirrored on and

@@ -159,6 +159,16 @@ _SIGS = {
     "tiler_interframe_correlation": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
     "tiler_interframe_correlation_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "tiler_find_keyframes": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "tiler_load_dims": (c_int, [c_int, c_int, P(c_int), P(c_int)]),
+    "tiler_load_frames_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.c_int64, ctypes.c_int64, c_void_p,
+                                      c_void_p]),
+    "tiler_load_frames": (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.c_int64, ctypes.c_int64, c_void_p]),
+    "tiler_store_frames_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                       c_void_p]),
+    "tiler_store_frames": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, ctypes.c_int64, ctypes.c_int64]),
+    "tiler_load_clip_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.c_int64, ctypes.c_int64, c_void_p,
+                                    c_void_p, c_void_p, c_void_p]),
+    "tiler_debug_load_chunk": (c_int, [ctypes.c_int64]),
     "tiler_render_frames": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                     c_void_p, c_int, c_void_p, c_void_p]),

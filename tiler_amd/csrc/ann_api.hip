@@ -27,6 +27,7 @@
 #include "kmeans.hpp"
 #include "detmath.hpp"
 #include "keyframes.hpp"
+#include "load.hpp"
 #include "lzma_match.hpp"
 #include "kmodes.hpp"
 #include "nn_search.hpp"
@@ -1491,6 +1492,59 @@ int tiler_interframe_correlation_dev(const int32_t *d_rgb, int F, int tm_w, int 
 int tiler_find_keyframes(const double *corr, int F, int tile_map_size, int32_t *kf_of_frame) {
     return find_keyframes(corr, F, tile_map_size, kf_of_frame);
 }
+
+// ---- raster ingest: the arguments are checked on the host before the device is touched ----
+int tiler_load_dims(int src_w, int src_h, int *tm_w, int *tm_h) { return load_dims(src_w, src_h, tm_w, tm_h); }
+
+int tiler_load_frames_dev(const uint8_t *d_src, int fmt, int F, int src_w, int src_h, int64_t pitch,
+                          int64_t frame_stride, int32_t *d_rgb, void *stream) {
+    if (load_check("tiler_load_frames_dev", d_src, fmt, F, src_w, src_h, pitch, frame_stride, d_rgb, true)) return -1;
+    if (F == 0) return 0;
+    if (!ensure_init()) return -1;
+    DevScope ds(ptr_device(d_src));
+    return load_frames_dev(d_src, fmt, F, src_w, src_h, pitch, frame_stride, d_rgb, (hipStream_t)stream);
+}
+
+int tiler_load_frames(const uint8_t *src, int fmt, int F, int src_w, int src_h, int64_t pitch, int64_t frame_stride,
+                      int32_t *rgb) {
+    if (load_check("tiler_load_frames", src, fmt, F, src_w, src_h, pitch, frame_stride, rgb, false)) return -1;
+    if (F == 0) return 0;
+    if (!ensure_init()) return -1;
+    return load_frames_host(src, fmt, F, src_w, src_h, pitch, frame_stride, rgb);
+}
+
+int tiler_store_frames_dev(const int32_t *d_rgb, int F, int tm_w, int tm_h, int fmt, uint8_t *d_dst, int64_t pitch,
+                           int64_t frame_stride, void *stream) {
+    if (store_check("tiler_store_frames_dev", d_rgb, F, tm_w, tm_h, fmt, d_dst, pitch, frame_stride, true)) return -1;
+    if (F == 0) return 0;
+    if (!ensure_init()) return -1;
+    DevScope ds(ptr_device(d_rgb));
+    return store_frames_dev(d_rgb, F, tm_w, tm_h, fmt, d_dst, pitch, frame_stride, (hipStream_t)stream);
+}
+
+int tiler_store_frames(const int32_t *rgb, int F, int tm_w, int tm_h, int fmt, uint8_t *dst, int64_t pitch,
+                       int64_t frame_stride) {
+    if (store_check("tiler_store_frames", rgb, F, tm_w, tm_h, fmt, dst, pitch, frame_stride, false)) return -1;
+    if (F == 0) return 0;
+    if (!ensure_init()) return -1;
+    return store_frames_host(rgb, F, tm_w, tm_h, fmt, dst, pitch, frame_stride);
+}
+
+int tiler_load_clip_dev(const uint8_t *d_src, int fmt, int F, int src_w, int src_h, int64_t pitch,
+                        int64_t frame_stride, int32_t *d_rgb, double *corr, int32_t *kf_of_frame, void *stream) {
+    if (load_check("tiler_load_clip_dev", d_src, fmt, F, src_w, src_h, pitch, frame_stride, d_rgb, true)) return -1;
+    if ((F > 0 && !kf_of_frame) || (F > 1 && !corr)) {
+        set_error("tiler_load_clip_dev: corr or kf_of_frame is null");
+        return -1;
+    }
+    if (F == 0) return 0;
+    if (!ensure_init()) return -1;
+    DevScope ds(ptr_device(d_src));
+    return load_clip_dev(d_src, fmt, F, src_w, src_h, pitch, frame_stride, d_rgb, corr, kf_of_frame,
+                         (hipStream_t)stream);
+}
+
+int tiler_debug_load_chunk(int64_t frames) { return load_chunk_debug(frames); }
 
 int tiler_render_frames(int F, int Q, const int32_t *tile, const int32_t *pal, const uint8_t *hm, const uint8_t *vm,
                         const int32_t *sm_tile, const int32_t *sm_pal, const uint8_t *sm_hm, const uint8_t *sm_vm,

@@ -47,6 +47,15 @@ def load_and_dither(frames, tm_w: int, tm_h: int, palettes_fn=None, n_palettes: 
     return video_from_dither(frames, kf_start, pals, cents, dith, dither_tiles, palsize)
 
 
+def load_and_dither_raster(images, fmt: str = "rgb24", **kw) -> Video:
+    """load_and_dither over pictures as a decoder leaves them: uint8 [F][H][W][3|4] in `fmt` ("rgb24", "bgr24",
+    "bgra32", "rgba32"), tiled on the GPU as LoadFrame cuts them (tiler_amd.load.frames_to_tiles); **kw goes to
+    load_and_dither."""
+    from .load import frames_to_tiles
+    frames, tm_w, tm_h = frames_to_tiles(images, fmt)
+    return load_and_dither(frames, tm_w, tm_h, **kw)
+
+
 class Encoder:
     """frames: the global frame indices this encoder holds the frames and tilemaps of (sorted, whole keyframes;
     None = all).  The tileset (palpix, flags, Active, UseCount) is always the whole clip's.  Tilemap arrays are
@@ -308,6 +317,17 @@ class Encoder:
             return render_frames(self.tile, self.pal, self.hm, self.vm, *tail, sm["tile"], sm["pal"], sm["hm"],
                                  sm["vm"], sm["smoothed"])
         return render_frames(sm["tile"], sm["pal"], sm["hm"], sm["vm"], *tail)
+
+    def render_raster(self, fmt: str = "rgb24", *, width: int, height: int, on_screen: bool = False):
+        """render() as pictures an image writer or video encoder takes: (uint8 [frames][height][width][3|4] in `fmt`,
+        X = 0xFF, invalid [frames]).  width, height: the screen in pixels, as save_stream takes them (the encoder
+        holds only their product in tiles)."""
+        from .load import tiles_to_frames
+        tm_w, tm_h = int(width) // 8, int(height) // 8
+        if tm_w < 1 or tm_h < 1 or tm_w * tm_h != self.tiles_per_frame:
+            raise ValueError(f"render_raster: {width} x {height} is not the {self.tiles_per_frame} tiles of a frame")
+        rgb, invalid = self.render(on_screen)
+        return tiles_to_frames(rgb, tm_w, tm_h, fmt), invalid
 
     def _stream_frames(self, data):
         """The held frames as a GTM player shows them: `data` (.gtm bytes, a path or a binary file holding the whole

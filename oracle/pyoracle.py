@@ -14,6 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "liboracle.so")
 REF_LIB = os.path.join(HERE, "_ref", "libkmodes_ref.so")
 REF_DLQUANT_LIB = os.path.join(HERE, "_ref", "libdlquant_ref.so")
+REF_PLAYER_JS = ("lzma.js", "lzma.shim.js", "gtm.player.js")
 
 _o = None
 
@@ -391,6 +392,39 @@ def ref_dlquant_lib():
     r.ref_dl3quant.restype = ctypes.c_int
     r.ref_dl3quant.argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
     return r
+
+
+def ref_player_dir():
+    """The directory of the reference's browser player (lzma.js, lzma.shim.js, gtm.player.js) if the reference tree
+    and node are both here; else None."""
+    import shutil
+    d = os.path.join(os.environ.get("TILER_REFERENCE", "/root/reference"), "decoders", "htmljs")
+    if shutil.which("node") is None or not all(os.path.isfile(os.path.join(d, f)) for f in REF_PLAYER_JS):
+        return None
+    return d
+
+
+def ref_player(gtm):
+    """A .gtm file (bytes, or a path) played by the reference's own player under oracle/ref_player.js: a dict of
+    frames, width, height (tiles), frame_sha256 (per frame, of the RGBA framebuffer bytes), clip_sha256 (of all the
+    framebuffers end to end), stalls and errors (its console.error lines).  None where ref_player_dir() is None."""
+    import json
+    import subprocess
+    import tempfile
+    d = ref_player_dir()
+    if d is None:
+        return None
+    with tempfile.TemporaryDirectory() as tmp:
+        path = gtm
+        if isinstance(gtm, (bytes, bytearray, memoryview)):
+            path = os.path.join(tmp, "clip.gtm")
+            with open(path, "wb") as f:
+                f.write(gtm)
+        r = subprocess.run(["node", os.path.join(HERE, "ref_player.js"), d, os.fspath(path)], capture_output=True,
+                           text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"ref_player.js failed ({r.returncode}): {r.stderr[-2000:]}")
+    return json.loads(r.stdout)
 
 
 def ref_dl3quant(ref, pixels, quant_to=16, bpc=7):

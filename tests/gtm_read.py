@@ -116,9 +116,11 @@ def read_gtm(oracle, data: bytes) -> GTM:
 
 
 def render(g: GTM):
-    """RGBA frames [F][H*8][W*8][4] as the player draws them (skips keep the previous pixels)."""
+    """RGBA frames [F][H*8][W*8][4] as the player draws them (skips keep the previous pixels; a position never drawn
+    shows the canvas as redimFrame fills it, opaque black, gtm.player.js:150-153)."""
     H, W = g.height, g.width
     img = np.zeros((H * 8, W * 8, 4), np.uint8)
+    img[..., 3] = 255
     out = []
     for items, pal, _ in g.frames:
         for yx in np.nonzero(items[:, 0] >= 0)[0]:

@@ -8,12 +8,10 @@ import numpy as np
 import pytest
 
 import gtm_read
-from gtm_cases import Z, assemble, strip_header, written_stream
+from gtm_cases import BLACK, never_drawn_stream, palette_reload_stream, strip_header, written_stream
 from tiler_amd import gtm
 
 pytestmark = pytest.mark.gpu
-
-BLACK = 0xFF000000
 
 
 def _reference(oracle, data):
@@ -67,19 +65,7 @@ def test_carry_over_a_palette_reload(gpu, oracle):
     """Hand-built (the writer never produces it): keyframe 1 reloads palette 0 with other colours and its first
     frame skips a block of positions.  Those keep keyframe 0's pixels -- drawn through the old colours -- while the
     positions redrawn with palette 0 get the new ones."""
-    rng = np.random.default_rng(3)
-    W, H, T = 4, 2, 6
-    tiles = rng.integers(0, 16, (T, 64))
-    old = rng.integers(0, 1 << 24, 16) | BLACK
-    new = (old ^ 0x00FFFFFF)
-    other = rng.integers(0, 1 << 24, 16) | BLACK
-    k0 = Z().dims(W, H, T).tileset(tiles).palette(0, old).palette(1, other)
-    for q in range(8):
-        k0.item(q % T, pal=q & 1, h=q & 1, v=(q >> 1) & 1)
-    k0.end(1)
-    k1 = Z().palette(0, new).item(5, pal=0).skip(4).item(4, pal=0, h=1).item(3, pal=1).item(2, pal=0, v=1).end(0)
-    k1.skip(2).item(1, pal=0).skip(5).end(1)
-    data = assemble([k0.b, k1.b], [0, 1, 3], W, H)
+    data, W, H, old, new = palette_reload_stream()
     ref = _reference(oracle, data)
     with gtm.Stream(data) as st:
         assert st.pal_rows == 3 and np.array_equal(st.palettes[2], new.astype(np.uint32))
@@ -97,15 +83,8 @@ def test_carry_over_a_palette_reload(gpu, oracle):
 def test_never_drawn_positions(gpu):
     """Hand-built: the first frame skips 5 positions -- opaque black, undrawn 5; a later frame draws 2 of them and
     undrawn is 3 from that frame on."""
-    rng = np.random.default_rng(4)
-    W, H, T = 4, 2, 3
-    pal = rng.integers(1, 1 << 24, 16) | BLACK
-    z = Z().dims(W, H, T).tileset(rng.integers(0, 16, (T, 64))).palette(0, pal)
-    z.item(0).skip(3).item(1).skip(2).item(2).end(0)
-    z.skip(8).end(0)
-    z.skip(2).item(1).skip(2).item(0, h=1).skip(2).end(0)
-    z.skip(8).end(1)
-    with gtm.Stream(assemble([z.b], [0, 4], W, H)) as st:
+    data, W, H = never_drawn_stream()
+    with gtm.Stream(data) as st:
         assert list(st.frame_flags()[2]) == [5, 5, 3, 3]
         for chunk in (1, 4):
             st.rewind()

@@ -669,9 +669,13 @@ int tiler_gtm_stream_sizes(tiler_gtm *h, uint64_t *raw, uint64_t *comp);
  * writer's streams; never drawn: 0xFF000000) -- mask the top byte to compare with the project's 0x00BBGGRR frames.
  * layout TILER_GTM_TILES: d_rgb[n][Q][64], the project's tile-major frames (tiler_frame_quality_dev takes them);
  * TILER_GTM_RASTER: d_rgb[n][8 height][8 width], what a player shows.  d_rgb is 16-byte aligned.  d_undrawn[n]
- * (optional) = the frame's count of never-drawn positions.  Plays sequentially: the handle keeps each position's last
- * drawn item between calls (seeking to a keyframe is not offered: it is exact only for streams whose keyframes start
- * with no skipped item, a property of the writer, not of the format).  Returns the frames produced (fewer than n at
+ * (optional) = the frame's count of never-drawn positions.  Plays on from the handle's position: the handle keeps each
+ * position's last drawn item between calls.  After tiler_gtm_seek the next play call first rebuilds those items for
+ * the new position, drawing nothing: it copies the nearest row at or before it of a checkpoint index -- the carried
+ * items at the first frame of every s-th keyframe, s the smallest stride whose rows fit 256 MiB of HBM, built on the
+ * device by the first call that needs it -- and walks the items between, at most s keyframes' frames however far into
+ * the stream.  The picture is exactly what a play from frame 0 shows there, for any well-formed stream (keyframes
+ * that begin with skipped items or reload a palette index included).  Returns the frames produced (fewer than n at
  * the end of the stream, then 0), or -1. */
 #define TILER_GTM_TILES 0
 #define TILER_GTM_RASTER 1
@@ -679,6 +683,24 @@ int64_t tiler_gtm_play_dev(tiler_gtm *h, int64_t n, int layout, int32_t *d_rgb, 
 /* The same into host arrays. */
 int64_t tiler_gtm_play(tiler_gtm *h, int64_t n, int layout, int32_t *rgb, int32_t *undrawn);
 int tiler_gtm_rewind(tiler_gtm *h); /* the next play call starts at frame 0 with nothing drawn */
+/* The next play call starts at `frame`, 0 <= frame <= frames (frames: the end, the next play returns 0).  Host code,
+ * needs no GPU; clears the state a failed play call leaves.  Another frame: -1, the error names it and the range, and
+ * the position stays.  Seeking to the current position changes nothing; tiler_gtm_seek(h, 0) is tiler_gtm_rewind. */
+int tiler_gtm_seek(tiler_gtm *h, int64_t frame);
+/* Random access: frames[0..n) in any order, repeats allowed -> request i's picture in d_rgb[i] (either layout, as
+ * play) and d_undrawn[i] (optional), exactly as a play from frame 0 shows that frame.  The position of sequential
+ * play and its carried items are not touched, and a failure does not disturb them.  Distinct frames are resolved
+ * once, each checkpoint interval is walked once.  Every index is checked before the device is touched: one outside
+ * [0, frames) is -1 naming the entry and its value; n = 0 returns 0 and needs no GPU.  Asynchronous on stream, on the
+ * handle's device, ordered behind the handle's earlier calls like play.  Returns n or -1. */
+int64_t tiler_gtm_frames_dev(tiler_gtm *h, const int64_t *frames, int64_t n, int layout, int32_t *d_rgb,
+                             int32_t *d_undrawn, void *stream);
+/* The same into host arrays. */
+int64_t tiler_gtm_frames(tiler_gtm *h, const int64_t *frames, int64_t n, int layout, int32_t *rgb, int32_t *undrawn);
+/* Tests: the items per pass of the seek and frames walks and the checkpoint index budget in bytes (0: the default, 2^22
+ * items and 256 MiB), for handles that build their index afterwards.  Sequential play keeps its own pass size.
+ * Negative: -1. */
+int tiler_debug_gtm_seek(int64_t pass_items, int64_t index_bytes);
 
 /* ---- GTM writing (SaveStream main.pas:4529-4763) -----------------------------------------------------
  * The SmoothedTileMaps of whole keyframes -> each keyframe's command stream, built on the GPU, LZMA-compressed on

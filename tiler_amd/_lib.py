@@ -224,6 +224,11 @@ _SIGS = {
     "tiler_gtm_play_dev": (ctypes.c_int64, [c_void_p, ctypes.c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "tiler_gtm_play": (ctypes.c_int64, [c_void_p, ctypes.c_int64, c_int, c_void_p, c_void_p]),
     "tiler_gtm_rewind": (c_int, [c_void_p]),
+    "tiler_gtm_seek": (c_int, [c_void_p, ctypes.c_int64]),
+    "tiler_gtm_frames_dev": (ctypes.c_int64, [c_void_p, c_void_p, ctypes.c_int64, c_int, c_void_p, c_void_p,
+                                              c_void_p]),
+    "tiler_gtm_frames": (ctypes.c_int64, [c_void_p, c_void_p, ctypes.c_int64, c_int, c_void_p, c_void_p]),
+    "tiler_debug_gtm_seek": (c_int, [ctypes.c_int64, ctypes.c_int64]),
     "tiler_gtm_commands_dev": (c_int, [P(GtmSource), c_void_p, c_size_t, c_void_p, c_void_p]),
     "tiler_gtm_commands": (c_int, [P(GtmSource), c_void_p, c_size_t, c_void_p]),
     "tiler_gtm_streams_dev": (c_int, [P(GtmSource), c_int, c_void_p, c_size_t, c_void_p, P(c_size_t), c_void_p]),

@@ -1891,6 +1891,33 @@ int tiler_gtm_rewind(tiler_gtm *h) {
     return p ? player_rewind(p) : -1;
 }
 
+int tiler_gtm_seek(tiler_gtm *h, int64_t frame) {
+    Player *p = gtm_handle(h, "gtm_seek");
+    return p ? player_seek(p, frame) : -1;
+}
+
+// the frame list is checked before the device is: a bad index or an empty list needs none
+int64_t tiler_gtm_frames_dev(tiler_gtm *h, const int64_t *frames, int64_t n, int layout, int32_t *d_rgb,
+                             int32_t *d_undrawn, void *stream) {
+    Player *p = gtm_handle(h, "gtm_frames");
+    if (!p || player_check_frames(p, frames, n, layout)) return -1;
+    if (n == 0) return 0;
+    if (!ensure_init()) return -1;
+    DevScope ds(ptr_device(d_rgb));
+    return player_frames_dev(p, frames, n, layout, d_rgb, d_undrawn, (hipStream_t)stream);
+}
+
+int64_t tiler_gtm_frames(tiler_gtm *h, const int64_t *frames, int64_t n, int layout, int32_t *rgb, int32_t *undrawn) {
+    Player *p = gtm_handle(h, "gtm_frames");
+    if (!p || player_check_frames(p, frames, n, layout)) return -1;
+    if (n == 0) return 0;
+    if (!ensure_init()) return -1;
+    DevScope ds(player_device(p) >= 0 ? player_device(p) : ptr_device(nullptr));
+    return player_frames_host(p, frames, n, layout, rgb, undrawn);
+}
+
+int tiler_debug_gtm_seek(int64_t pass_items, int64_t index_bytes) { return player_seek_debug(pass_items, index_bytes); }
+
 // ---- GTM writing: the command words on the device, LZMA and the container on the host (tiler_gtm_assemble: no device)
 int tiler_gtm_commands_dev(const tiler_gtm_source_t *src, uint8_t *d_raw, size_t cap, int64_t *raw_off, void *stream) {
     if (!ensure_init()) return -1;

@@ -17,4 +17,17 @@ int player_device(const Player *p);  // -1 until the first play call
 int64_t player_play_dev(Player *p, int64_t n, int layout, int32_t *d_rgb, int32_t *d_undrawn, hipStream_t stream);
 int64_t player_play_host(Player *p, int64_t n, int layout, int32_t *rgb, int32_t *undrawn);
 int player_rewind(Player *p);
+// host only: the next play call starts at `frame` (0 <= frame <= frames) on the framebuffer a play from frame 0 shows
+// there; it rebuilds the carried items from the checkpoint index (play.hip) before its first pass
+int player_seek(Player *p, int64_t frame);
+// host only: n >= 0, a known layout and every frames[i] inside the stream, else -1 naming the entry
+int player_check_frames(Player *p, const int64_t *frames, int64_t n, int layout);
+// frames[0..n), any order, repeats allowed: request i into d_rgb[i] and d_undrawn[i] (or NULL), as play shows them;
+// neither the next frame nor the carried items of sequential play are touched.  Returns n or -1
+int64_t player_frames_dev(Player *p, const int64_t *frames, int64_t n, int layout, int32_t *d_rgb, int32_t *d_undrawn,
+                          hipStream_t stream);
+int64_t player_frames_host(Player *p, const int64_t *frames, int64_t n, int layout, int32_t *rgb, int32_t *undrawn);
+// the pass size (items) of the seek paths and the index budget (bytes), 0 = the default; for handles that build their
+// index afterwards
+int player_seek_debug(int64_t pass_items, int64_t index_bytes);
 }  // namespace tiler

@@ -331,8 +331,10 @@ class Encoder:
 
     def _stream_frames(self, data):
         """The held frames as a GTM player shows them: `data` (.gtm bytes, a path or a binary file holding the whole
-        clip) played on the GPU, the rows of `frame_idx` kept -> (rgb [frames][Q][64] int32 0x00BBGGRR, the top byte
-        of the stream's 0xAABBGGRR masked off; undrawn [frames])."""
+        clip), the frames of `frame_idx` alone drawn on the GPU (gtm.Stream.frames: the player's checkpoint index gives
+        the pixels a skipped position carries, so the frames this encoder does not hold are neither drawn nor
+        copied) -> (rgb [frames][Q][64] int32 0x00BBGGRR, the top byte of the stream's 0xAABBGGRR masked off;
+        undrawn [frames])."""
         Q = self.tiles_per_frame
         with gtm.Stream(data) as st:
             if st.positions != Q or st.frames != self.n_frames:
@@ -341,11 +343,10 @@ class Encoder:
             rgb = np.zeros((self.frames, Q, 64), np.int32)
             undrawn = np.zeros(self.frames, np.int32)
             chunk = max(1, (1 << 27) // (Q * 256))
-            for f0 in range(0, st.frames, chunk):  # a skipped position carries pixels: every frame is played
-                got, und = st.play(chunk, "tiles", chunk)
-                rows = np.nonzero((self.frame_idx >= f0) & (self.frame_idx < f0 + got.shape[0]))[0]
-                rgb[rows] = (got[self.frame_idx[rows] - f0] & 0x00FFFFFF).astype(np.int32)
-                undrawn[rows] = und[self.frame_idx[rows] - f0]
+            for r0 in range(0, self.frames, chunk):
+                got, und = st.frames(self.frame_idx[r0:r0 + chunk], "tiles", chunk)
+                rgb[r0:r0 + chunk] = (got & 0x00FFFFFF).astype(np.int32)
+                undrawn[r0:r0 + chunk] = und
         return rgb, undrawn
 
     def verify_stream(self, data=None, *, width: int, height: int, fps: float = 24.0) -> dict:

@@ -23,6 +23,7 @@ from __future__ import annotations
 import ctypes
 import os
 import struct
+import weakref
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -389,10 +390,29 @@ def lzma_decode(data: bytes, max_raw_bytes: int = MAX_RAW_BYTES) -> tuple:
         cap = min(max_raw_bytes, max(n.value, 4 * cap))
 
 
+class _Frames(int):
+    """Stream.frames: the stream's frame count -- an int, as it has always been -- which, called with a list of
+    frame indices, draws those frames (Stream._frames has the contract).  One name serves both because the count
+    was there first and `frames(indices)` is what a reader of the C ABI (tiler_gtm_frames) looks for."""
+
+    def __new__(cls, count: int, draw):
+        self = int.__new__(cls, count)
+        self._draw = weakref.WeakMethod(draw)  # no cycle: an unreferenced Stream still closes at once
+        return self
+
+    def __call__(self, indices, layout: str = "tiles", chunk: int | None = None) -> tuple:
+        draw = self._draw()
+        if draw is None:
+            raise TilerError("the stream is gone")
+        return draw(indices, layout, chunk)
+
+
 class Stream:
     """A .gtm file opened for playback: bytes, a path or a binary file.  Parsing (header, LZMA, command tokens) is
-    host code and needs no GPU; `play` needs the device.  Stricter than the reference JS player: malformed command
-    streams raise TilerError naming the rule, the frame and the position (include/tiler_ann.h)."""
+    host code and needs no GPU; `play`, `frames` and `frame` need the device.  Stricter than the reference JS player:
+    malformed command streams raise TilerError naming the rule, the frame and the position (include/tiler_ann.h).
+    `frames` is the frame count and, called with indices, random access: frames(indices, layout="tiles", chunk=None)
+    -> (rgb, undrawn)."""
 
     def __init__(self, source, threads: int = 0, max_raw_bytes: int = MAX_RAW_BYTES):
         if isinstance(source, str) or hasattr(source, "__fspath__"):
@@ -409,7 +429,7 @@ class Stream:
         info = GtmInfo()
         check(self._lib.tiler_gtm_info(self._h, ctypes.byref(info)), "tiler_gtm_info")
         self.width, self.height, self.frame_ns = info.width, info.height, info.frame_ns
-        self.frames, self.keyframes, self.palsize = info.frames, info.keyframes, info.palsize
+        self.frames, self.keyframes, self.palsize = _Frames(info.frames, self._frames), info.keyframes, info.palsize
         self.n_tiles, self.pal_rows, self.n_streams = info.tiles, info.pal_rows, info.streams
         self.header = ({"AverageBytesPerSec": info.avg_bytes_per_sec, "KFMaxBytesPerSec": info.kf_max_bytes_per_sec}
                        if info.has_header else None)
@@ -529,6 +549,52 @@ class Stream:
 
     def rewind(self):
         check(self._lib.tiler_gtm_rewind(self._handle()), "tiler_gtm_rewind")
+
+    def seek(self, frame: int):
+        """The next play starts at `frame` (0 .. frames; frames = the end) and shows exactly what a play from frame 0
+        shows there.  Needs no GPU itself; the play that follows walks at most a checkpoint stride of keyframes
+        (include/tiler_ann.h), never the frames before.  Another frame raises TilerError and leaves the position."""
+        check(self._lib.tiler_gtm_seek(self._handle(), int(frame)), "tiler_gtm_seek")
+
+    def _frames(self, indices, layout: str = "tiles", chunk: int | None = None) -> tuple:
+        """Stream.frames(indices, layout, chunk).  The frames `indices` (any order, repeats allowed) as play shows them, without moving next_frame: (rgb
+        [len(indices)] + play's frame shape, undrawn [len(indices)]), row i = frame indices[i].  Drawn `chunk`
+        requests per call (default: about 128 MiB of output).  An index outside the stream raises TilerError before
+        anything is drawn."""
+        if layout not in LAYOUTS:
+            raise ValueError("frames: layout is 'tiles' or 'raster'")
+        idx = np.ascontiguousarray(np.asarray(indices, np.int64).reshape(-1))
+        n, Q = idx.size, self.positions
+        chunk = max(1, (1 << 27) // max(Q * 256, 1)) if chunk is None else int(chunk)
+        if chunk <= 0:
+            raise ValueError("frames: chunk must be positive")
+        if ((idx < 0) | (idx >= self.frames)).any():  # the ABI's error for the whole list: no earlier chunk is drawn
+            check(self._lib.tiler_gtm_frames(self._handle(), _vp(idx), n, LAYOUTS[layout], None, None),
+                  "tiler_gtm_frames")
+        rgb = np.zeros((n, Q * 64), np.uint32)
+        undrawn = np.zeros(n, np.int32)
+        for at in range(0, n, chunk):
+            m = min(chunk, n - at)
+            got = check(self._lib.tiler_gtm_frames(self._handle(), _vp(idx[at:]), m, LAYOUTS[layout], _vp(rgb[at:]),
+                                                   _vp(undrawn[at:])), "tiler_gtm_frames")
+            if got != m:
+                raise TilerError(f"tiler_gtm_frames produced {got} of {m} frames")
+        shape = (n, Q, 64) if layout == "tiles" else (n, self.height * 8, self.width * 8)
+        return rgb.reshape(shape), undrawn
+
+    def frame(self, f: int, layout: str = "tiles") -> np.ndarray:
+        """Frame f alone ([Q][64] or [8 height][8 width]); next_frame stays."""
+        return self.frames([f], layout)[0][0]
+
+    def frames_dev(self, indices, d_rgb: int, layout: str = "tiles", d_undrawn: int = 0, stream=None) -> int:
+        """`frames` into HBM (device pointers; d_rgb 16-byte aligned, len(indices) frames), asynchronous on `stream`;
+        the indices are host values.  Returns len(indices)."""
+        idx = np.ascontiguousarray(np.asarray(indices, np.int64).reshape(-1))
+        return check(self._lib.tiler_gtm_frames_dev(self._handle(), _vp(idx), idx.size, LAYOUTS[layout],
+                                                    ctypes.c_void_p(int(d_rgb)) if d_rgb else None,
+                                                    ctypes.c_void_p(int(d_undrawn)) if d_undrawn else None,
+                                                    ctypes.c_void_p(int(stream)) if stream else None),
+                     "tiler_gtm_frames_dev")
 
 
 def load_stream(path) -> Stream:

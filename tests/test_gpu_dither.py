@@ -1,9 +1,12 @@
 """GPU parity of the Dither step per tile (DitherTile, Thomas Knoll mixing + PrepareTileMirrors) against the CPU
 restatement: palette indices and mirror flags bit-exact, including palettes with duplicate colours and distinct
-colours of equal luma (the reference QuickSort's tie order), palette sizes 4/8/16 and ragged tile counts."""
+colours of equal luma (the reference QuickSort's tie order), palette sizes 4/8/16 and ragged tile counts; then
+saturated tiles against palettes at the opposite corner of the cube, palettes of one colour or one luma, sorted
+palettes with ties, and the flat and mirror-symmetric tiles whose quadrant sums tie (tests/dither_extremes.py)."""
 import numpy as np
 import pytest
 
+import dither_extremes as dx
 from tiler_amd import synth
 from tiler_amd._lib import TilerError
 from tiler_amd.dither import dither_tiles
@@ -92,3 +95,17 @@ def test_dither_yliluoma_rejects_bad_input(gpu):
             dither_tiles(rgb, pal_of, np.zeros((1, 16), np.int32), yliluoma_mix=mixed)
     with pytest.raises(TilerError):
         dither_tiles(rgb, pal_of, np.zeros((1, 17), np.int32), yliluoma_mix=4)   # more than 16 palette entries
+
+
+@pytest.mark.parametrize("mixed", [0, 1, 4, 16], ids=["thomas_knoll", "yliluoma1", "yliluoma4", "yliluoma16"])
+@pytest.mark.parametrize("size", [2, 4, 16])
+def test_dither_extremes(gpu, oracle, size, mixed):
+    """15 tiles x 6 palette kinds at the stated integer bounds and at the ties of the sort and of the mirror choice;
+    that the inputs reach those ties is asserted from the restatement's output first."""
+    rgb, pal_of, pals, tname, kind = dx.cases(size)
+    o = oracle.dither_tiles_yl(rgb, pal_of, pals, mixed) if mixed else oracle.dither_tiles_tk(rgb, pal_of, pals)
+    dx.check_preconditions(size, o, tname, kind)
+    g = dither_tiles(rgb, pal_of, pals, yliluoma_mix=mixed)
+    for a, b, what in zip(g, o, ("palpix", "hm", "vm")):
+        bad = np.flatnonzero((a != b).reshape(a.shape[0], -1).any(1))
+        assert bad.size == 0, (what, [(tname[i], kind[i]) for i in bad[:6]])

@@ -59,3 +59,38 @@ def test_4k_frames_beyond_reference_cap(gpu, oracle):
     g = interframe_correlation(frames, 480, 270)
     o = oracle.interframe_corr_batch(frames, 480, 270)
     assert np.array_equal(g.view(np.uint64), o.view(np.uint64))
+
+
+# stages of 9 tile rows over the 24 w h tile rows of a frame (3 channels x 8 h screen rows x w tiles), fetched through
+# a register ring two stages deep: (tm_w, tm_h, ceil(24 w h / 9))
+NARROW = [(1, 1, 3), (1, 4, 11), (2, 2, 11), (2, 1, 6), (13, 1, 35)]
+
+
+@pytest.mark.parametrize("tm_w,tm_h,stages", NARROW)
+def test_correlation_odd_stage_counts_and_narrow_tilemaps(gpu, oracle, tm_w, tm_h, stages):
+    """Every stage count of the shapes above leaves a ragged last stage (24 w h is no multiple of 9); 3, 11 and 35 are
+    odd, so the ring's second slot is the one past the end; widths 1 and 2 make the producers' cursor wrap several
+    screen rows per 9-row step."""
+    assert stages == -(-24 * tm_w * tm_h // 9) and (24 * tm_w * tm_h) % 9
+    F = 5
+    rng = np.random.default_rng(tm_w * 17 + tm_h)
+    frames = synth.rgb_pack(*rng.integers(0, 256, (3, F, tm_w * tm_h, 64))).astype(np.int32)
+    frames[3] = frames[2] ^ (rng.random(frames[2].shape) < 0.1)  # one near-identical pair among unrelated frames
+    g = interframe_correlation(frames, tm_w, tm_h)
+    o = oracle.interframe_corr_batch(frames, tm_w, tm_h)
+    assert g.shape == o.shape == (F - 1,)
+    assert np.array_equal(g.view(np.uint64), o.view(np.uint64))
+    assert o[2] > 0.9 > np.abs(o[[0, 1, 3]]).max()  # the result depends on which frames are paired
+
+
+@pytest.mark.parametrize("F", [15, 16, 17, 30, 31])
+def test_correlation_frame_counts_at_workgroup_edges(gpu, oracle, F):
+    """A workgroup owns 15 frames and its lane 15 feeds lane 14 the next workgroup's first frame: 15 | 16 | 17 and
+    30 | 31 put the last frame, and the last pair, on either side of that seam."""
+    rng = np.random.default_rng(F)
+    frames = synth.rgb_pack(*rng.integers(0, 256, (3, F, 12, 64))).astype(np.int32)
+    g = interframe_correlation(frames, 4, 3)
+    o = oracle.interframe_corr_batch(frames, 4, 3)
+    assert g.shape == o.shape == (F - 1,)
+    assert np.array_equal(g.view(np.uint64), o.view(np.uint64))
+    assert np.unique(o).size == F - 1  # every pair has its own value: a shifted or repeated pair would show

@@ -2,7 +2,8 @@
 every (keyframe, palette) pair at once, CompareCMULHS order) bit-exact against the CPU restatement
 (oracle/palette.c) -- palettes, use counts and DLv3 colour-table sizes -- on textured / gradient / flat tiles,
 empty pairs, pairs with fewer colours than the palette, skipped (inactive / out-of-range) tiles and lookup bpc
-4..8.  The oracle is unpinned against the reference DLL (quantizer.c is not buildable here)."""
+4..8.  The oracle's dl3quant is pinned to the reference's own quantizer.c by test_dl3_ref.py.  The k-means of the
+chain is checked at its edges in test_gpu_kmeans_edges.py."""
 import numpy as np
 import pytest
 
@@ -109,7 +110,8 @@ def test_lab_descriptor_bit_exact(gpu, oracle, gamma):
 @pytest.mark.parametrize("n,k", [(3000, 8), (2500, 70), (200, 128), (50, 64)])
 def test_kmeans_bit_exact(gpu, oracle, n, k):
     """Seeding, every Lloyd step, the final labels and centroids, and the iteration count equal the restatement's
-    (k > 64 exercises the two-chunk assignment; n < k duplicates centres)."""
+    (the assignment takes the centroids 32 at a time: k = 70 runs three chunks, k = 128 four; n < k duplicates
+    centres)."""
     from tiler_amd.palette import kmeans
     rng = np.random.default_rng(n + k)
     centers = rng.normal(0, 10, (max(2, k // 2), 192))
@@ -142,3 +144,67 @@ def test_generate_palettes_chain_bit_exact(gpu, oracle):
     o = oracle.generate_palettes(frames, kf, 8)
     for a, b, name in zip(g, o, ("palettes", "centroids", "dith", "use_count")):
         assert np.array_equal(a, b), name
+
+
+def _degenerate_clip():
+    """Three keyframes of 2 frames x 120 tiles (10 wide, 12 high): textured; all black (a fade); letterboxed -- the top
+    and bottom four tile rows black, the middle four textured."""
+    rng = np.random.default_rng(51)
+    Q = 120
+    textured = synth.keyframe_frames(rng, 2, Q)
+    black = np.zeros((2, Q, 64), np.int32)
+    letterbox = synth.keyframe_frames(rng, 2, Q)
+    letterbox[:, :40] = 0
+    letterbox[:, 80:] = 0
+    return np.concatenate([textured, black, letterbox]), np.array([0, 2, 4, 6]), Q
+
+
+def test_degenerate_clip_chain_bit_exact(gpu, oracle):
+    """The palette half and the per-tile dither over a clip with a black keyframe and a letterboxed one: k-means on
+    equal descriptors, seven palettes without a tile, palettes of one colour."""
+    from tiler_amd.dither import dither_tiles
+    from tiler_amd.palette import generate_palettes
+    frames, kf, Q = _degenerate_clip()
+    P = 8
+    o = oracle.generate_palettes(frames, kf, P)
+    assert (o[3][1] == 0).sum() == P - 1 and o[3][1].max() == 2 * Q  # the black keyframe: one palette has every tile
+    assert (o[0][1] == 0).all()                                      # and every palette of it is black
+    g = generate_palettes(frames, kf, P)
+    for a, b, name in zip(g, o, ("palettes", "centroids", "dith", "use_count")):
+        assert a.shape == b.shape and np.array_equal(a, b), name
+    assert np.array_equal(g[1].view(np.uint64), o[1].view(np.uint64))
+    pal_of = (np.repeat(np.arange(3), 2 * Q) * P + o[2]).astype(np.int32)
+    rgb = frames.reshape(-1, 64)
+    od = oracle.dither_tiles_tk(rgb, pal_of, o[0].reshape(3 * P, 16))
+    assert not od[0][2 * Q:4 * Q].any() and not od[1][2 * Q:4 * Q].any() and not od[2][2 * Q:4 * Q].any()
+    gd = dither_tiles(rgb, pal_of, g[0].reshape(3 * P, 16))
+    for a, b, name in zip(gd, od, ("palpix", "hm", "vm")):
+        assert np.array_equal(a, b), name
+
+
+def test_degenerate_clip_chain_value_at_risk(gpu, oracle):
+    """The same clip with chkUseDL3 off.  The value-at-risk path has no answer for a palette without a tile (the
+    reference reads CMUsage[0] of an empty list): the black keyframe makes product and restatement fail alike, naming
+    the same pair.  The textured and the letterboxed keyframe then go through, compared as test_gpu_palette_var.py
+    compares them."""
+    import var_palette_ref as ref
+    from tiler_amd.palette import finish_quantize_palette, generate_palettes, prepare_dither_tiles
+    frames, kf, Q = _degenerate_clip()
+    P = 8
+    lab = [prepare_dither_tiles(frames[kf[k]:kf[k + 1]].reshape(-1, 64), P)[0] for k in range(3)]
+    assert [np.unique(v).size for v in lab] == [P, 1, P] and not lab[1].any()
+    acc0 = np.full(3 * P, ref.fpc_round(2 * Q * 64 * 0.9), np.int32)
+    pair_of = (np.repeat(np.arange(3), 2 * Q) * P + np.concatenate(lab)).astype(np.int32)
+    with pytest.raises(ValueError, match="pair 9 "):  # keyframe 1, palette 1: the first without a tile
+        ref.quantize_palettes_var(frames.reshape(-1, 64), pair_of, 3 * P, P, acc0, 16)
+    with pytest.raises(gpu.TilerError, match="pair 9 "):
+        generate_palettes(frames, kf, P, use_dl3=False, pal_var=0.9)
+    two = np.concatenate([frames[0:2], frames[4:6]])
+    pal, cent, dith, uc = generate_palettes(two, np.array([0, 2, 4]), P, use_dl3=False, pal_var=0.9)
+    for k, src in enumerate((0, 2)):
+        rgb = two[2 * k:2 * k + 2].reshape(-1, 64)
+        c = prepare_dither_tiles(rgb, P)[1]
+        o_pal, o_uc, _ = ref.quantize_palettes_var(rgb, lab[src], P, P, acc0[:P], 16)
+        w_pal, w_dith, w_cent, lut = finish_quantize_palette(o_pal, o_uc, lab[src], c)
+        assert np.array_equal(pal[k], w_pal) and np.array_equal(dith[k * 2 * Q:(k + 1) * 2 * Q], w_dith)
+        assert np.array_equal(cent[k].view(np.uint64), w_cent.view(np.uint64)) and np.array_equal(uc[k][lut], o_uc)

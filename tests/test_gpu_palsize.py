@@ -10,6 +10,7 @@ import functools
 import numpy as np
 import pytest
 
+import dither_extremes as dx
 import palsize_ref
 from tiler_amd import synth
 from tiler_amd._lib import TilerError
@@ -68,6 +69,20 @@ def test_dither_yliluoma_bit_exact(gpu, oracle, size, mixed):
     for a, b, what in zip(g, o, ("palpix", "hm", "vm")):
         assert np.array_equal(a, b), (what, int(np.count_nonzero(a != b)))
     assert int(g[0].max()) > 16
+
+
+@pytest.mark.parametrize("mixed", [0, 1, 4, 16], ids=["thomas_knoll", "yliluoma1", "yliluoma4", "yliluoma16"])
+@pytest.mark.parametrize("size", [32, 64])
+def test_dither_extremes(gpu, oracle, size, mixed):
+    """The _big kernels on tests/dither_extremes.py: saturated tiles against the opposite corner, palettes of one
+    colour or one luma, sorted palettes with ties, flat and mirror-symmetric tiles whose quadrant sums tie."""
+    rgb, pal_of, pals, tname, kind = dx.cases(size)
+    o = oracle.dither_tiles_yl(rgb, pal_of, pals, mixed) if mixed else oracle.dither_tiles_tk(rgb, pal_of, pals)
+    dx.check_preconditions(size, o, tname, kind)
+    g = dither_tiles(rgb, pal_of, pals, yliluoma_mix=mixed)
+    for a, b, what in zip(g, o, ("palpix", "hm", "vm")):
+        bad = np.flatnonzero((a != b).reshape(a.shape[0], -1).any(1))
+        assert bad.size == 0, (what, [(tname[i], kind[i]) for i in bad[:6]])
 
 
 @pytest.mark.parametrize("size", [17, 24, 48])

@@ -164,7 +164,7 @@ int tiler_set_gamma(double g0, double g1); /* gGamma main.pas:586 / 1441-1447; r
  * summed milliseconds and launch count of one kernel family ("psyv", "nn_prep", "nn_shortlist",
  * "nn_rescore", "nn_exact", "smooth", "kmodes", "render", "quality", "reload_match", "unique_insert", "unique_last",
  * "unique_merge", "unique_zero", "ft_dedup": FrameTiling's duplicate-tile passes and scatter, "reindex_count",
- * "reindex_active", "reindex_order", "reindex_gather", "reindex_remap", "load_frames", "store_frames").  Reading
+ * "reindex_active", "reindex_order", "reindex_gather", "reindex_remap", "load_frames", "store_frames", "load_frames_scaled").  Reading
  * synchronises the recorded events. */
 int tiler_timing_enable(int on);
 double tiler_timing_get(const char *kernel, int *launches);
@@ -453,6 +453,40 @@ int tiler_load_clip_dev(const uint8_t *d_src, int fmt, int F, int src_w, int src
 /* Test hook (process-wide): frames per staging chunk of tiler_load_frames / tiler_store_frames; 0 restores the
  * default (the 256 MiB rule above).  Results are identical for every value.  0 / -1 (frames < 0). */
 int tiler_debug_load_chunk(int64_t frames);
+
+/* ---- Load-step input scaling (cbxScaling main.pas:4780-4782, 1042, main.lfm:524-545) fused with the tile cut ----
+ * The reference's Load step has ffmpeg resize every picture (scale=iw*S:ih*S:flags=lanczos, S one of 0.25, 0.375,
+ * 0.5, 0.75, 1, 1.5, 2) before ReframeUI crops it.  Here the resize runs on the device in front of the tile cut.
+ * Parity with swscale's fixed-point Lanczos is NOT pinned: the arithmetic is Pillow's 8-bit
+ * Image.resize(size, Image.LANCZOS), bit for bit -- one pass per axis, the horizontal one first, a pass skipped when
+ * its axis keeps its size, an 8-bit clipped picture between the passes; per axis scale = in / out,
+ * support = 3 * max(scale, 1), taps L((x + xmin - center + 0.5) / max(scale, 1)) with L(t) = sinc(t) sinc(t / 3),
+ * normalised in double on the host, rounded to 22 fractional bits, result clip((2^21 + sum pixel * tap) >> 22).
+ * out = floor(src * scale) per axis (exact for the seven factors).  -1 when scale is not finite and positive, or a
+ * side comes out below 8 or above 16384. */
+int tiler_scale_dims(int src_w, int src_h, double scale, int *out_w, int *out_h);
+/* The tap table of one axis (host code; needs no GPU): returns ksize = 2 * ceil(3 * max(in / out, 1)) + 1 and fills
+ * bounds[out][2] = (xmin, xmax) and taps[out][ksize] (tap x of output xx weighs source sample xmin + x; 0 past xmax).
+ * cap = the int32 that taps holds (at least out * ksize).  bounds and taps both NULL: only ksize.  in and out are
+ * 1 .. 2^24.  -1 on error. */
+int tiler_scale_coeffs(int n_in, int n_out, int32_t *bounds, int32_t *taps, int64_t cap);
+/* tiler_load_frames_dev / tiler_load_frames / tiler_load_clip_dev on the pictures resized to out_w x out_h (the
+ * size, not the factor: ffmpeg's rounding of a fractional product is the caller's choice).  The tilemap is
+ * tiler_load_dims(out_w, out_h); only the top-left tm_w*8 x tm_h*8 pixels of the resized picture are computed, and
+ * source rows and columns beyond the last kept pixel's taps are never read.  out_w, out_h are 8 .. 16384 and at
+ * least src / 8 per axis.  With out_w == src_w and out_h == src_h each call is its unscaled form.  Every argument
+ * is checked before anything is launched: -1 with tiler_last_error() naming it.  F = 0 returns 0.  The tap tables
+ * and the intermediate picture of a (src, out) size live in a small cache inside the library; calls on different
+ * streams are ordered on the device where they share it. */
+int tiler_load_frames_scaled_dev(const uint8_t *d_src, int fmt, int F, int src_w, int src_h, int64_t pitch,
+                                 int64_t frame_stride, int out_w, int out_h, int32_t *d_rgb, void *stream);
+int tiler_load_frames_scaled(const uint8_t *src, int fmt, int F, int src_w, int src_h, int64_t pitch,
+                             int64_t frame_stride, int out_w, int out_h, int32_t *rgb);
+/* Correlations and the keyframe split come from the scaled frames, as the reference takes them from the scaled
+ * pictures.  Returns the keyframe count or -1. */
+int tiler_load_clip_scaled_dev(const uint8_t *d_src, int fmt, int F, int src_w, int src_h, int64_t pitch,
+                               int64_t frame_stride, int out_w, int out_h, int32_t *d_rgb, double *corr,
+                               int32_t *kf_of_frame, void *stream);
 
 /* ---- Quality readout (Render main.pas:3305-3493, lblCorrel main.pas:3470-3489) ------------------------
  * Render's destination frame from the tilemaps, as Render draws it with dithered, reduced and mirrored on and

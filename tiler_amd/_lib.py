@@ -169,6 +169,14 @@ _SIGS = {
     "tiler_load_clip_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.c_int64, ctypes.c_int64, c_void_p,
                                     c_void_p, c_void_p, c_void_p]),
     "tiler_debug_load_chunk": (c_int, [ctypes.c_int64]),
+    "tiler_scale_dims": (c_int, [c_int, c_int, ctypes.c_double, P(c_int), P(c_int)]),
+    "tiler_scale_coeffs": (c_int, [c_int, c_int, c_void_p, c_void_p, ctypes.c_int64]),
+    "tiler_load_frames_scaled_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.c_int64, ctypes.c_int64,
+                                             c_int, c_int, c_void_p, c_void_p]),
+    "tiler_load_frames_scaled": (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.c_int64, ctypes.c_int64, c_int,
+                                         c_int, c_void_p]),
+    "tiler_load_clip_scaled_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.c_int64, ctypes.c_int64,
+                                           c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "tiler_render_frames": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                     c_void_p, c_int, c_void_p, c_void_p]),

@@ -28,6 +28,7 @@
 #include "detmath.hpp"
 #include "keyframes.hpp"
 #include "load.hpp"
+#include "scale.hpp"
 #include "lzma_match.hpp"
 #include "kmodes.hpp"
 #include "nn_search.hpp"
@@ -1545,6 +1546,54 @@ int tiler_load_clip_dev(const uint8_t *d_src, int fmt, int F, int src_w, int src
 }
 
 int tiler_debug_load_chunk(int64_t frames) { return load_chunk_debug(frames); }
+
+// ---- Lanczos input scaling in front of the tile cut ----
+int tiler_scale_dims(int src_w, int src_h, double scale, int *out_w, int *out_h) {
+    return scale_dims(src_w, src_h, scale, out_w, out_h);
+}
+
+int tiler_scale_coeffs(int n_in, int n_out, int32_t *bounds, int32_t *taps, int64_t cap) {
+    return scale_coeffs(n_in, n_out, bounds, taps, cap);
+}
+
+int tiler_load_frames_scaled_dev(const uint8_t *d_src, int fmt, int F, int src_w, int src_h, int64_t pitch,
+                                 int64_t frame_stride, int out_w, int out_h, int32_t *d_rgb, void *stream) {
+    const char *who = "tiler_load_frames_scaled_dev";
+    if (load_check(who, d_src, fmt, F, src_w, src_h, pitch, frame_stride, d_rgb, true)) return -1;
+    if (scale_check(who, src_w, src_h, out_w, out_h)) return -1;
+    if (F == 0) return 0;
+    if (!ensure_init()) return -1;
+    DevScope ds(ptr_device(d_src));
+    return load_frames_scaled_dev(d_src, fmt, F, src_w, src_h, pitch, frame_stride, out_w, out_h, d_rgb,
+                                  (hipStream_t)stream);
+}
+
+int tiler_load_frames_scaled(const uint8_t *src, int fmt, int F, int src_w, int src_h, int64_t pitch,
+                             int64_t frame_stride, int out_w, int out_h, int32_t *rgb) {
+    const char *who = "tiler_load_frames_scaled";
+    if (load_check(who, src, fmt, F, src_w, src_h, pitch, frame_stride, rgb, false)) return -1;
+    if (scale_check(who, src_w, src_h, out_w, out_h)) return -1;
+    if (F == 0) return 0;
+    if (!ensure_init()) return -1;
+    return load_frames_scaled_host(src, fmt, F, src_w, src_h, pitch, frame_stride, out_w, out_h, rgb);
+}
+
+int tiler_load_clip_scaled_dev(const uint8_t *d_src, int fmt, int F, int src_w, int src_h, int64_t pitch,
+                               int64_t frame_stride, int out_w, int out_h, int32_t *d_rgb, double *corr,
+                               int32_t *kf_of_frame, void *stream) {
+    const char *who = "tiler_load_clip_scaled_dev";
+    if (load_check(who, d_src, fmt, F, src_w, src_h, pitch, frame_stride, d_rgb, true)) return -1;
+    if (scale_check(who, src_w, src_h, out_w, out_h)) return -1;
+    if ((F > 0 && !kf_of_frame) || (F > 1 && !corr)) {
+        set_error("tiler_load_clip_scaled_dev: corr or kf_of_frame is null");
+        return -1;
+    }
+    if (F == 0) return 0;
+    if (!ensure_init()) return -1;
+    DevScope ds(ptr_device(d_src));
+    return load_clip_scaled_dev(d_src, fmt, F, src_w, src_h, pitch, frame_stride, out_w, out_h, d_rgb, corr,
+                                kf_of_frame, (hipStream_t)stream);
+}
 
 int tiler_render_frames(int F, int Q, const int32_t *tile, const int32_t *pal, const uint8_t *hm, const uint8_t *vm,
                         const int32_t *sm_tile, const int32_t *sm_pal, const uint8_t *sm_hm, const uint8_t *sm_vm,

@@ -24,6 +24,7 @@
 #include <string>
 
 #include "keyframes.hpp"
+#include "raster_dev.hpp"
 #include "stage.hpp"
 
 namespace tiler {
@@ -71,21 +72,6 @@ __device__ __forceinline__ SpanAt span_of_block(int tm_w, int tm_h, int spans) {
     a.tx0 = sp * SPAN_TILES;
     a.nt = min(SPAN_TILES, tm_w - a.tx0);
     return a;
-}
-
-// dword j of a span row whose first byte is al[s]: whole where it lies inside [s, s + n), else its bytes that do
-__device__ __forceinline__ uint32_t fetch_dword(const uint8_t *al, int s, int n, int j, int nd) {
-    uint32_t v = 0;
-    const int lo = 4 * j;
-    if (j < nd) {
-        if (lo >= s && lo + 4 <= s + n) {
-            v = *(const uint32_t *)(al + lo);
-        } else {
-            for (int b = 0; b < 4; b++)
-                if (lo + b >= s && lo + b < s + n) v |= (uint32_t)al[lo + b] << (8 * b);
-        }
-    }
-    return v;
 }
 
 template <int BPP>
@@ -320,11 +306,12 @@ struct Dense {
     Dense(int fmt, int tm_w, int tm_h) : row((int64_t)tm_w * 8 * pix_bytes(fmt)), pitch((row + 3) & ~3ll),
                                          frame(pitch * tm_h * 8), rows(tm_h * 8) {}
 };
-static int chunk_frames(int F, const Dense &d, int64_t tile_bytes) {
+int load_chunk_frames(int F, int64_t frame_bytes) {
     const int64_t forced = g_chunk_frames.load();
-    const int64_t n = forced > 0 ? forced : std::max<int64_t>(1, LOAD_CHUNK_BYTES / (d.frame + tile_bytes));
+    const int64_t n = forced > 0 ? forced : std::max<int64_t>(1, LOAD_CHUNK_BYTES / frame_bytes);
     return (int)std::min<int64_t>(n, F);
 }
+static int chunk_frames(int F, const Dense &d, int64_t tile_bytes) { return load_chunk_frames(F, d.frame + tile_bytes); }
 
 int load_frames_host(const uint8_t *src, int fmt, int F, int src_w, int src_h, int64_t pitch, int64_t frame_stride,
                      int32_t *rgb) {

@@ -39,6 +39,8 @@ int load_clip_dev(const uint8_t *d_src, int fmt, int F, int src_w, int src_h, in
                   int32_t *d_rgb, double *corr, int32_t *kf_of_frame, hipStream_t stream);
 // Test hook: frames per chunk of the host forms (0: the default, LOAD_CHUNK_BYTES of picture + tile bytes)
 int load_chunk_debug(int64_t frames);
+// Frames per staging chunk of a host form whose frame takes frame_bytes of device memory (picture + tiles)
+int load_chunk_frames(int F, int64_t frame_bytes);
 
 constexpr int64_t LOAD_CHUNK_BYTES = 256ll << 20;
 }  // namespace tiler

@@ -47,12 +47,12 @@ def load_and_dither(frames, tm_w: int, tm_h: int, palettes_fn=None, n_palettes: 
     return video_from_dither(frames, kf_start, pals, cents, dith, dither_tiles, palsize)
 
 
-def load_and_dither_raster(images, fmt: str = "rgb24", **kw) -> Video:
+def load_and_dither_raster(images, fmt: str = "rgb24", scale=None, size=None, **kw) -> Video:
     """load_and_dither over pictures as a decoder leaves them: uint8 [F][H][W][3|4] in `fmt` ("rgb24", "bgr24",
-    "bgra32", "rgba32"), tiled on the GPU as LoadFrame cuts them (tiler_amd.load.frames_to_tiles); **kw goes to
-    load_and_dither."""
+    "bgra32", "rgba32"), tiled on the GPU as LoadFrame cuts them (tiler_amd.load.frames_to_tiles); scale= (cbxScaling)
+    or size=(out_w, out_h) resizes them there first; **kw goes to load_and_dither."""
     from .load import frames_to_tiles
-    frames, tm_w, tm_h = frames_to_tiles(images, fmt)
+    frames, tm_w, tm_h = frames_to_tiles(images, fmt, scale=scale, size=size)
     return load_and_dither(frames, tm_w, tm_h, **kw)
 
 

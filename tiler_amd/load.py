@@ -43,6 +43,26 @@ def load_dims(src_w: int, src_h: int):
     return w.value, h.value
 
 
+def scale_dims(src_w: int, src_h: int, scale: float):
+    """cbxScaling: the size ffmpeg's scale=iw*S:ih*S leaves, (floor(src_w * S), floor(src_h * S)); exact for the
+    reference's seven factors 0.25, 0.375, 0.5, 0.75, 1, 1.5, 2."""
+    w, h = ctypes.c_int(0), ctypes.c_int(0)
+    check(_load_lib().tiler_scale_dims(int(src_w), int(src_h), float(scale), ctypes.byref(w), ctypes.byref(h)),
+          "tiler_scale_dims")
+    return w.value, h.value
+
+
+def _out_size(src_w: int, src_h: int, scale, size):
+    """The size of the resized picture from the scale= / size= keywords; neither: the source's (no scaling)."""
+    if scale is not None and size is not None:
+        raise ValueError("give scale or size, not both")
+    if size is not None:
+        return int(size[0]), int(size[1])
+    if scale is not None:
+        return scale_dims(src_w, src_h, scale)
+    return int(src_w), int(src_h)
+
+
 def _pictures(images, fmt: str):
     """images as uint8 [F][H][W][bpp] with the pixel dimensions dense; rows and frames keep their strides (no copy of
     a clip sliced out of a larger array).  Returns (array, pitch, frame_stride)."""
@@ -64,29 +84,45 @@ def _pictures(images, fmt: str):
     return a, pitch, frame_stride
 
 
-def frames_to_tiles(images, fmt: str = "rgb24"):
+def frames_to_tiles(images, fmt: str = "rgb24", scale=None, size=None):
     """Pictures uint8 [F][H][W][3|4] (or one [H][W][3|4]) -> (frames [F][Q][64] int32, tm_w, tm_h): the top-left
     tm_w*8 x tm_h*8 pixels of every picture, tiled on the GPU.  The array may be non-contiguous in the row and frame
-    dimensions: pitch and frame stride are its strides."""
+    dimensions: pitch and frame stride are its strides.  scale= (cbxScaling's factor) or size=(out_w, out_h) resizes
+    the pictures first, on the GPU, as Pillow's 8-bit Image.resize(size, LANCZOS) does (tiler_load_frames_scaled)."""
     code = _fmt(fmt)
     a, pitch, frame_stride = _pictures(images, fmt)
     F, H, W, _ = a.shape
-    tm_w, tm_h = load_dims(W, H)
+    if scale is None and size is None:
+        tm_w, tm_h = load_dims(W, H)
+        frames = np.empty((F, tm_w * tm_h, 64), np.int32)
+        check(_load_lib().tiler_load_frames(_vp(a), code, F, W, H, pitch, frame_stride, _vp(frames)),
+              "tiler_load_frames")
+        return frames, tm_w, tm_h
+    out_w, out_h = _out_size(W, H, scale, size)
+    tm_w, tm_h = load_dims(out_w, out_h)
     frames = np.empty((F, tm_w * tm_h, 64), np.int32)
-    check(_load_lib().tiler_load_frames(_vp(a), code, F, W, H, pitch, frame_stride, _vp(frames)), "tiler_load_frames")
+    check(_load_lib().tiler_load_frames_scaled(_vp(a), code, F, W, H, pitch, frame_stride, out_w, out_h, _vp(frames)),
+          "tiler_load_frames_scaled")
     return frames, tm_w, tm_h
 
 
 def frames_to_tiles_dev(d_src: int, F: int, src_w: int, src_h: int, d_rgb: int, fmt: str = "rgb24", pitch=None,
-                        frame_stride=None, stream=None):
+                        frame_stride=None, stream=None, scale=None, size=None):
     """Device-pointer form (ints are HBM addresses; d_rgb 16-byte aligned), asynchronous on `stream`.  pitch defaults
-    to src_w * bpp, frame_stride to src_h * pitch.  Returns (tm_w, tm_h)."""
+    to src_w * bpp, frame_stride to src_h * pitch.  scale= / size= as in frames_to_tiles
+    (tiler_load_frames_scaled_dev).  Returns (tm_w, tm_h)."""
     code = _fmt(fmt)
     pitch = src_w * _BPP[fmt] if pitch is None else int(pitch)
     frame_stride = src_h * pitch if frame_stride is None else int(frame_stride)
-    check(_load_lib().tiler_load_frames_dev(_dp(d_src), code, int(F), int(src_w), int(src_h), pitch, frame_stride,
-                                            _dp(d_rgb), _dp(stream)), "tiler_load_frames_dev")
-    return load_dims(src_w, src_h)
+    if scale is None and size is None:
+        check(_load_lib().tiler_load_frames_dev(_dp(d_src), code, int(F), int(src_w), int(src_h), pitch, frame_stride,
+                                                _dp(d_rgb), _dp(stream)), "tiler_load_frames_dev")
+        return load_dims(src_w, src_h)
+    out_w, out_h = _out_size(src_w, src_h, scale, size)
+    check(_load_lib().tiler_load_frames_scaled_dev(_dp(d_src), code, int(F), int(src_w), int(src_h), pitch,
+                                                   frame_stride, out_w, out_h, _dp(d_rgb), _dp(stream)),
+          "tiler_load_frames_scaled_dev")
+    return load_dims(out_w, out_h)
 
 
 def tiles_to_frames(frames, tm_w: int, tm_h: int, fmt: str = "rgb24", pitch=None, out=None) -> np.ndarray:
@@ -119,23 +155,31 @@ def tiles_to_frames_dev(d_rgb: int, F: int, tm_w: int, tm_h: int, d_dst: int, fm
                                              frame_stride, _dp(stream)), "tiler_store_frames_dev")
 
 
-def load_clip(images, fmt: str = "rgb24"):
+def load_clip(images, fmt: str = "rgb24", scale=None, size=None):
     """The Load step in one call (tiler_load_clip_dev): the pictures go to HBM once, are tiled there, and the
     inter-frame correlations and the keyframe split come from the tiles where they lie.  Returns (frames [F][Q][64]
     int32, tm_w, tm_h, kf_of_frame [F], kf_start [KF+1], corr [F-1]).  The whole clip is resident for the call; a
-    clip beyond HBM goes through frames_to_tiles and keyframes.detect_keyframes instead."""
+    clip beyond HBM goes through frames_to_tiles and keyframes.detect_keyframes instead.  scale= / size= as in
+    frames_to_tiles: the correlations and the split are then those of the resized frames
+    (tiler_load_clip_scaled_dev)."""
     import torch
     code = _fmt(fmt)
     a, _, _ = _pictures(images, fmt)
     F, H, W, bpp = a.shape
-    tm_w, tm_h = load_dims(W, H)
+    out_w, out_h = _out_size(W, H, scale, size)
+    tm_w, tm_h = load_dims(out_w, out_h)
     d_src = torch.from_numpy(a).cuda()  # dense on the device whatever the host strides
     d_rgb = torch.empty((F, tm_w * tm_h, 64), dtype=torch.int32, device="cuda")
     corr = np.zeros(max(0, F - 1), np.float64)
     kf = np.zeros(F, np.int32)
     torch.cuda.current_stream().synchronize()
-    check(_load_lib().tiler_load_clip_dev(_dp(d_src.data_ptr()), code, F, W, H, W * bpp, H * W * bpp,
-                                          _dp(d_rgb.data_ptr()), _vp(corr), _vp(kf), None), "tiler_load_clip_dev")
+    if scale is None and size is None:
+        check(_load_lib().tiler_load_clip_dev(_dp(d_src.data_ptr()), code, F, W, H, W * bpp, H * W * bpp,
+                                              _dp(d_rgb.data_ptr()), _vp(corr), _vp(kf), None), "tiler_load_clip_dev")
+    else:
+        check(_load_lib().tiler_load_clip_scaled_dev(_dp(d_src.data_ptr()), code, F, W, H, W * bpp, H * W * bpp,
+                                                     out_w, out_h, _dp(d_rgb.data_ptr()), _vp(corr), _vp(kf), None),
+              "tiler_load_clip_scaled_dev")
     return d_rgb.cpu().numpy(), tm_w, tm_h, kf, keyframe_starts(kf), corr
 
 

@@ -111,6 +111,11 @@ int tiler_set_scan_limits(int max_k1, int max_k8);
 /* Test hook (process-wide): on != 0 makes ANN's pruning check vouch for no result, so every query of every kd-order
  * search takes the exact replay of annkSearch (kd_replay_kernel); answers are identical either way.  0. */
 int tiler_debug_force_replay(int on);
+/* Test hook (read-only): how the handle's last ann_kdtree_pri_search_batch answered its queries at eps = 0 --
+ * out[0] decided from the exact tie set, out[1] the priority search replayed in full, out[2] the heap order alone
+ * simulated up to the first tied leaf.  All three are 0 after a call with eps != 0 (every query is replayed without
+ * the resolve step), on a handle without a tree and before the first call.  0 / -1. */
+int tiler_debug_pri_outcomes(ann_kdtree *akd, int64_t out[3]);
 /* Test / bench hook (process-wide): on = 0 switches off the k = 1 generic shortlist's exact insertion gate (the query's
  * best key so far bounds what its lists may need), for A/B timing; answers are identical either
  * way.  Default 1.  0. */

@@ -122,6 +122,13 @@ class KDTree:
               "ann_kdtree_pri_search_batch")
         return idx, err
 
+    def pri_outcomes(self) -> tuple:
+        """Queries of the last pri_search_batch answered (from the tie set, by the full replay, by the heap-order
+        simulation) at eps = 0; all 0 otherwise (tiler_debug_pri_outcomes)."""
+        out = (ctypes.c_int64 * 3)()
+        check(self._lib.tiler_debug_pri_outcomes(self.handle, out), "tiler_debug_pri_outcomes")
+        return tuple(int(v) for v in out)
+
     def search_batch_dev(self, q_ptr: int, nq: int, k: int, idx_ptr: int, err_ptr: int, stream: int = 0):
         check(self._lib.ann_kdtree_search_batch_dev(self.handle, ctypes.c_void_p(q_ptr), nq, k,
                                                     ctypes.c_void_p(idx_ptr), ctypes.c_void_p(err_ptr),

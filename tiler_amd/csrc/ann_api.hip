@@ -336,6 +336,7 @@ struct ann_kdtree {
     size_t cap_pri = 0;
     void *d_pri_aux = nullptr;    // kd_pri_resolve scratch + the replay flags
     size_t cap_pri_aux = 0;
+    long long pri_out[3] = {};    // queries of the last pri_search_batch per resolve flag (tiler_debug_pri_outcomes)
     PrepScratch *prep = nullptr;  // tiler_prepare_frame_tiling_dev scratch (on the global dataset's handle)
     int dev = 0;                  // the device the handle's index, stream and buffers live on
     hipEvent_t maps_ev = nullptr; // recorded after tiler_prepare_frame_tiling_dev wrote the TRTo maps (on its stream)
@@ -942,10 +943,17 @@ int ann_kdtree_pri_search_batch(ann_kdtree *t, const float *q, int nq, float eps
         return -1;
     }
     if (!ensure_init()) return -1;
-    if (!t->ix->kd) return ann_kdtree_search_multi_batch(t, q, nq, 1, eps, idx, err);
+    if (!t->ix->kd) {
+        {
+            std::lock_guard<std::mutex> lk(t->ix->mu);
+            t->pri_out[0] = t->pri_out[1] = t->pri_out[2] = 0;
+        }
+        return ann_kdtree_search_multi_batch(t, q, nq, 1, eps, idx, err);
+    }
     DevScope ds(t->dev);
     NNIndex *ix = t->ix;
     std::lock_guard<std::mutex> lk(ix->mu);
+    t->pri_out[0] = t->pri_out[1] = t->pri_out[2] = 0;
     if (nq == 0) return 0;
     if (ix->n == 0) {
         for (int i = 0; i < nq; i++) {
@@ -974,6 +982,8 @@ int ann_kdtree_pri_search_batch(ann_kdtree *t, const float *q, int nq, float eps
         TILER_HIP_CHECK(hipMalloc(&t->d_pri_aux, aux));
         t->cap_pri_aux = aux;
     }
+    std::vector<uint8_t> h_flag(eps == 0.0f ? (size_t)chunk : 0);  // a chunk's flags (tiler_debug_pri_outcomes)
+    long long outcomes[3] = {};
     for (int q0 = 0; q0 < nq; q0 += chunk) {
         const int c = std::min(chunk, nq - q0);
         TILER_HIP_CHECK(hipMemcpyAsync(t->d_q, q + (size_t)q0 * ix->d, (size_t)c * ix->d * sizeof(float),
@@ -991,12 +1001,27 @@ int ann_kdtree_pri_search_batch(ann_kdtree *t, const float *q, int nq, float eps
             return -1;
         TILER_HIP_CHECK(hipMemcpyAsync(idx + q0, t->d_idx, (size_t)c * sizeof(int), hipMemcpyDeviceToHost, t->stream));
         TILER_HIP_CHECK(hipMemcpyAsync(err + q0, t->d_err, (size_t)c * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+        if (flag) TILER_HIP_CHECK(hipMemcpyAsync(h_flag.data(), flag, (size_t)c, hipMemcpyDeviceToHost, t->stream));
         TILER_HIP_CHECK(hipStreamSynchronize(t->stream));
+        if (flag)
+            for (int i = 0; i < c; i++)
+                if (h_flag[i] < 3) outcomes[h_flag[i]]++;
     }
+    for (int i = 0; i < 3; i++) t->pri_out[i] = outcomes[i];
     // the heap scratch (up to 1 GiB) is not kept on the handle: several keyframe handles would each pin it
     (void)hipFree(t->d_pri);
     t->d_pri = nullptr;
     t->cap_pri = 0;
+    return 0;
+}
+
+int tiler_debug_pri_outcomes(ann_kdtree *t, int64_t out[3]) {
+    if (!t || !t->ix || !out) {
+        set_error("tiler_debug_pri_outcomes: invalid arguments");
+        return -1;
+    }
+    std::lock_guard<std::mutex> lk(t->ix->mu);
+    for (int i = 0; i < 3; i++) out[i] = t->pri_out[i];
     return 0;
 }
 

@@ -300,6 +300,12 @@ int tiler_debug_kmodes_ff_fallback(int on);
 /* Medoids of every bin's clusters (as tiler_kmodes_medoids per bin): medoid[sum k] bin-local rows. */
 int tiler_kmodes_medoids_batch(const uint8_t *X, const int32_t *bin_off, int nbins, const int32_t *k,
                                const int32_t *labels, const uint8_t *centroids, int32_t *medoid, int32_t *counts);
+/* The same with X / labels / centroids (X and centroids 16-byte aligned) and the outputs medoid[sum k] / counts[sum k]
+ * in HBM; bin_off / k are host arrays; labels must lie in [0, k) of their bin (not checked).  Nothing is decoded on
+ * the host, so a kernel can consume the result where it lies.  Synchronous on `stream`. */
+int tiler_kmodes_medoids_batch_dev(const uint8_t *d_X, const int32_t *bin_off, int nbins, const int32_t *k,
+                                   const int32_t *d_labels, const uint8_t *d_centroids, int32_t *d_medoid,
+                                   int32_t *d_counts, void *stream);
 
 /* ---- GlobalTiling, reload branch (ReloadPreviousTiling main.pas:4372-4470) ----
  * Batched GetMinMatchingDissim (kmodes.pas:598-604): rows[n][80] dataset lines of arbitrary bytes, group g = rows
@@ -407,6 +413,51 @@ int tiler_remap_items_dev(int32_t *d_tile, int64_t n_items, const int64_t *d_map
 /* Test hook (process-wide): the counting strategy of tiler_tile_use_count: 0 = per-workgroup LDS counters in windows
  * of 65,536 tiles, 1 = wave-combined global atomics, -1 = the default (by nt).  Results are identical.  0 / -1. */
 int tiler_debug_reindex(int strategy);
+
+/* ---- GlobalTiling, K-Modes branch (DoGlobalTiling main.pas:4256-4343, DoKModes 4195-4254) as one call ----
+ * The step between MakeTilesUnique and FinishMergeTiles over a tile list: palpix[nt][64], active[nt], use_count[nt]
+ * (int64) in and out, dith_pal[nt] (DitheringPalIndex) in, merge_index[nt] out.
+ *   1. the Active tiles are binned by dith_pal, ascending tile index inside a bin (TileIndices[signi]);
+ *   2. bin p of size n gets ClusterCount = ceil(EqualQualityTileCount(n) * desired / sum of EqualQualityTileCount)
+ *      (tiler_global_tiling_counts) and runs K-Modes iff n > ClusterCount;
+ *   3. its rows are the tiles' 80-byte dataset lines (tiler_tile_dataset_lines), its StartingPoint the LAST row of
+ *      minimal byte sum;
+ *   4. K-Modes of all such bins (tiler_kmodes_batch_dev with n_modalities = palsize) and their medoids;
+ *   5. every tile of a cluster with >= 2 members other than the cluster's medoid tile is merged into it (MergeTiles
+ *      main.pas:3688-3712, NewTile = nil): use_count summed into the medoid tile, active cleared, merge_index = the
+ *      medoid tile, palpix zeroed.  merge_index is -1 for every other tile.
+ * The call ends where FinishMergeTiles begins: apply merge_index with tiler_remap_items(..., keep_unmapped = 1).
+ * Optional host outputs, each [n_palettes], any may be NULL: bin_size[p] = the Active tiles of bin p; k[p] =
+ * round(ClusterCount) of every bin, run or not; start[p] = the bin-local StartingPoint, -restart for an empty bin
+ * (restart = cRandomKModesCount, 7, has no other effect).
+ * Limits, checked before the device is touched (-1): 0 <= nt < 2^31, 1 <= n_palettes <= 4096, 1 <= palsize <= 256,
+ * 1 <= desired <= 2^30.  Every tile with active != 0 must have dith_pal in [0, n_palettes) and all 64 bytes below
+ * palsize (the reference would index out of bounds): otherwise the tile is never used as an index, the call returns
+ * -1 and tiler_last_error() names the lowest such tile and what is wrong with it; inactive tiles may hold anything.
+ * nt = 0, no Active tile or no bin to run: 0, nothing merged, merge_index all -1.  The result does not depend on the
+ * order threads run in (integer atomics only).  On failure the host form leaves every caller array untouched; in the
+ * _dev form they are unspecified.
+ * _dev: the five arrays in HBM (palpix 16-byte aligned), bin_size / k / start host arrays, on `stream`.  It waits
+ * three times -- for the histogram and the error word, for the StartingPoints, and for the merges at the end --
+ * beside the waits of the K-Modes batch in between; the tile bytes never leave HBM. */
+int tiler_global_tiling(uint8_t *palpix, const int32_t *dith_pal, uint8_t *active, int64_t *use_count,
+                        int64_t *merge_index, int64_t nt, int n_palettes, int palsize, int desired, int restart,
+                        int32_t *bin_size, int32_t *k, int32_t *start);
+int tiler_global_tiling_dev(uint8_t *d_palpix, const int32_t *d_dith_pal, uint8_t *d_active, int64_t *d_use_count,
+                            int64_t *d_merge_index, int64_t nt, int n_palettes, int palsize, int desired, int restart,
+                            int32_t *bin_size, int32_t *k, int32_t *start, void *stream);
+/* The cluster counts alone (host code, no device): eq(n) = round(sqrt(n) * (ln(1 + n) * 1.4426950408889634079)), half
+ * to even (EqualQualityTileCount main.pas:722-725); share = desired / sum eq; k[p] = ceil(eq(bin_size[p]) * share);
+ * run[p] = bin_size[p] > k[p].  k / run may be NULL.  All bins empty: every k and run is 0.  -1 for a NULL or negative
+ * bin_size, n_palettes outside [1, 4096], desired outside [1, 2^30]. */
+int tiler_global_tiling_counts(const int32_t *bin_size, int n_palettes, int desired, int32_t *k, uint8_t *run);
+/* WriteTileDatasetLine (main.pas:4167-4183) of every tile: lines[nt][80] = the 64 indices, then the 16 zone flags
+ * count(idx * 16 div palsize == z) > palsize div 16 (the threshold is 0 for palsize < 16; an index whose zone is past
+ * the 16th is counted nowhere); pal_signi[nt] = GetTilePalZoneThres' return value, 64 - the largest zone count.
+ * Either output may be NULL.  1 <= palsize <= 256.  _dev: palpix and lines 16-byte aligned; synchronous. */
+int tiler_tile_dataset_lines(const uint8_t *palpix, int64_t nt, int palsize, uint8_t *lines, int32_t *pal_signi);
+int tiler_tile_dataset_lines_dev(const uint8_t *d_palpix, int64_t nt, int palsize, uint8_t *d_lines,
+                                 int32_t *d_pal_signi, void *stream);
 
 /* ---- Load-step keyframe detection (btnLoadClick main.pas:1099-1146) ----------------
  * frames[F][tm_h*tm_w][64] int32 0x00BBGGRR (TFrame.Tiles[].RGBPixels, tile-major, as FrameTiling takes

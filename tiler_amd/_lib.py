@@ -211,6 +211,15 @@ _SIGS = {
     "tiler_remap_items": (c_int, [c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int64, c_int]),
     "tiler_remap_items_dev": (c_int, [c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int64, c_int, c_void_p]),
     "tiler_debug_reindex": (c_int, [c_int]),
+    "tiler_global_tiling": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int, c_int,
+                                    c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "tiler_global_tiling_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int, c_int,
+                                        c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tiler_global_tiling_counts": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "tiler_tile_dataset_lines": (c_int, [c_void_p, ctypes.c_int64, c_int, c_void_p, c_void_p]),
+    "tiler_tile_dataset_lines_dev": (c_int, [c_void_p, ctypes.c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "tiler_kmodes_medoids_batch_dev": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p]),
     "tiler_debug_psyv_lane_items": (c_int, [ctypes.c_int64]),
     "tiler_lzma_encode": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_uint32, c_int, c_void_p, c_size_t,
                                   c_void_p]),

@@ -35,6 +35,7 @@
 #include "orbit.hpp"
 #include "psyv.hpp"
 #include "quality.hpp"
+#include "global_tiling.hpp"
 #include "reindex.hpp"
 #include "reload.hpp"
 #include "smooth.hpp"
@@ -1842,6 +1843,55 @@ int tiler_remap_items_dev(int32_t *d_tile, int64_t n_items, const int64_t *d_map
 }
 
 int tiler_debug_reindex(int strategy) { return reindex_debug(strategy); }
+
+// ---- GlobalTiling's K-Modes branch: plan, K-Modes, medoids and merges (global_tiling.hip) ----
+int tiler_global_tiling_counts(const int32_t *bin_size, int n_palettes, int desired, int32_t *k, uint8_t *run) {
+    return global_tiling_counts(bin_size, n_palettes, desired, k, run);  // host code: no device
+}
+
+int tiler_global_tiling(uint8_t *palpix, const int32_t *dith_pal, uint8_t *active, int64_t *use_count,
+                        int64_t *merge_index, int64_t nt, int n_palettes, int palsize, int desired, int restart,
+                        int32_t *bin_size, int32_t *k, int32_t *start) {
+    if (nt < 0 || nt >= (1ll << 31)) nt = -1;
+    if (global_tiling_check_args((long)nt, n_palettes, palsize, desired)) return -1;  // before the device is touched
+    if (!ensure_init()) return -1;
+    return global_tiling_host(palpix, dith_pal, active, use_count, merge_index, (long)nt, n_palettes, palsize, desired,
+                              restart, bin_size, k, start);
+}
+
+int tiler_global_tiling_dev(uint8_t *d_palpix, const int32_t *d_dith_pal, uint8_t *d_active, int64_t *d_use_count,
+                            int64_t *d_merge_index, int64_t nt, int n_palettes, int palsize, int desired, int restart,
+                            int32_t *bin_size, int32_t *k, int32_t *start, void *stream) {
+    if (nt < 0 || nt >= (1ll << 31)) nt = -1;
+    if (global_tiling_check_args((long)nt, n_palettes, palsize, desired)) return -1;
+    if (!ensure_init()) return -1;
+    DevScope ds(ptr_device(d_palpix));
+    return global_tiling_dev(d_palpix, d_dith_pal, d_active, d_use_count, d_merge_index, (long)nt, n_palettes, palsize,
+                             desired, restart, bin_size, k, start, (hipStream_t)stream);
+}
+
+int tiler_tile_dataset_lines(const uint8_t *palpix, int64_t nt, int palsize, uint8_t *lines, int32_t *pal_signi) {
+    if (nt < 0 || nt >= (1ll << 31)) nt = -1;
+    if (!ensure_init()) return -1;
+    return tile_dataset_lines_host(palpix, (long)nt, palsize, lines, pal_signi);
+}
+
+int tiler_tile_dataset_lines_dev(const uint8_t *d_palpix, int64_t nt, int palsize, uint8_t *d_lines,
+                                 int32_t *d_pal_signi, void *stream) {
+    if (nt < 0 || nt >= (1ll << 31)) nt = -1;
+    if (!ensure_init()) return -1;
+    DevScope ds(ptr_device(d_palpix));
+    return tile_dataset_lines_dev(d_palpix, (long)nt, palsize, d_lines, d_pal_signi, (hipStream_t)stream);
+}
+
+int tiler_kmodes_medoids_batch_dev(const uint8_t *d_X, const int32_t *bin_off, int nbins, const int32_t *k,
+                                   const int32_t *d_labels, const uint8_t *d_centroids, int32_t *d_medoid,
+                                   int32_t *d_counts, void *stream) {
+    if (!ensure_init()) return -1;
+    DevScope ds(ptr_device(d_X));
+    return kmodes_medoids_batch_devout(d_X, bin_off, nbins, k, d_labels, d_centroids, d_medoid, d_counts,
+                                       (hipStream_t)stream);
+}
 
 // ---- GTM playback: parsing and the getters are host code (no ensure_init); only the play calls need the device ----
 static Player *gtm_handle(tiler_gtm *h, const char *who) {

@@ -1697,6 +1697,21 @@ int kmodes_compute_dev(const uint8_t *d_X, int n, int k, int start_point, int n_
     return 0;
 }
 
+// kmb_medoid over a batch whose bin / cluster offsets already lie in HBM: d_best [K] packed (dissimilarity << 32 |
+// 0xFFFFFFFF - bin-local row) words, d_counts [K] members; both are initialised here.  Asynchronous on st.  0 / -1
+int kmodes_medoids_words_dev(const uint8_t *d_X, const int32_t *d_boff, const int32_t *d_koff, int nb, long N, long K,
+                             const int32_t *d_labels, const uint8_t *d_centroids, unsigned long long *d_best,
+                             int32_t *d_counts, hipStream_t st) {
+    if (K <= 0) return 0;
+    TILER_HIP_CHECK(hipMemsetAsync(d_best, 0xff, (size_t)K * 8, st));
+    TILER_HIP_CHECK(hipMemsetAsync(d_counts, 0, (size_t)K * 4, st));
+    if (N > 0)
+        hipLaunchKernelGGL(kmb_medoid, dim3((unsigned)std::min<long>(4096, (N + 255) / 256)), dim3(256), 0, st, d_X,
+                           d_boff, d_koff, nb, N, d_labels, d_centroids, d_best, d_counts);
+    TILER_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 int kmodes_medoids_batch_dev(const uint8_t *d_X, const int32_t *h_boff, int nb, const int32_t *h_k,
                              const int32_t *d_labels, const uint8_t *d_centroids, int32_t *h_medoid, int32_t *h_counts,
                              hipStream_t st) {
@@ -1708,15 +1723,11 @@ int kmodes_medoids_batch_dev(const uint8_t *d_X, const int32_t *h_boff, int nb, 
     TILER_HIP_CHECK(hipMalloc((void **)&buf, oKo + (nb + 1) * 4 + 256));
     int rc = -1;
     do {
-        if (hipMemsetAsync(buf + oB, 0xff, (size_t)K * 8, st) != hipSuccess) break;
-        if (hipMemsetAsync(buf + oN, 0, (size_t)K * 4, st) != hipSuccess) break;
         if (hipMemcpyAsync(buf + oBo, h_boff, (nb + 1) * 4, hipMemcpyHostToDevice, st) != hipSuccess) break;
         if (hipMemcpyAsync(buf + oKo, koff.data(), (nb + 1) * 4, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (N > 0)
-            hipLaunchKernelGGL(kmb_medoid, dim3((unsigned)std::min<long>(4096, (N + 255) / 256)), dim3(256), 0, st, d_X,
-                               (const int32_t *)(buf + oBo), (const int32_t *)(buf + oKo), nb, N, d_labels, d_centroids,
-                               (unsigned long long *)(buf + oB), (int32_t *)(buf + oN));
-        if (hipGetLastError() != hipSuccess) break;
+        if (kmodes_medoids_words_dev(d_X, (const int32_t *)(buf + oBo), (const int32_t *)(buf + oKo), nb, N, K, d_labels,
+                                     d_centroids, (unsigned long long *)(buf + oB), (int32_t *)(buf + oN), st))
+            break;
         std::vector<unsigned long long> b(K);
         if (hipMemcpyAsync(b.data(), buf + oB, (size_t)K * 8, hipMemcpyDeviceToHost, st) != hipSuccess) break;
         if (hipMemcpyAsync(h_counts, buf + oN, (size_t)K * 4, hipMemcpyDeviceToHost, st) != hipSuccess) break;

@@ -23,4 +23,9 @@ void kmodes_last_stats(long long *pairs, long long *steps);
 void kmodes_force_ff_fallback(int on);
 int kmodes_medoids_batch_host(const uint8_t *X, const int32_t *boff, int nb, const int32_t *k, const int32_t *labels,
                               const uint8_t *centroids, int32_t *medoid, int32_t *counts);
+// kmb_medoid with the bin offsets boff [nb + 1] / cluster offsets koff [nb + 1] in HBM: d_best [K] packed words
+// (dissimilarity << 32 | 0xFFFFFFFF - bin-local row), d_counts [K]; initialised here, asynchronous on st.  0 / -1
+int kmodes_medoids_words_dev(const uint8_t *d_X, const int32_t *d_boff, const int32_t *d_koff, int nb, long N, long K,
+                             const int32_t *d_labels, const uint8_t *d_centroids, unsigned long long *d_best,
+                             int32_t *d_counts, hipStream_t st);
 }  // namespace tiler

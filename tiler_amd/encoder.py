@@ -10,7 +10,8 @@ Each method is the reference procedure of the same name (file:line in its docstr
 through the C ABI, the rest is the reference's host bookkeeping -- MakeTilesUnique too unless the encoder is made
 with gpu_unique=True (tiler_make_tiles_unique; the same result), and Reindex's counts, order and TileMap remaps
 unless it is made with gpu_reindex=True (tiler_tile_use_count, tiler_reindex_tiles, tiler_gather_tiles,
-tiler_remap_items; the same result).  SURVEY.md 8(f)-1.
+tiler_remap_items; the same result), and GlobalTiling's binning, StartingPoints and merges unless it is made with
+gpu_global_tiling=True (tiler_global_tiling; the same result).  SURVEY.md 8(f)-1.
 """
 from __future__ import annotations
 
@@ -62,7 +63,7 @@ class Encoder:
     [len(frames)][Q]: row r is frame frames[r]."""
 
     def __init__(self, v: Video, palsize: int | None = None, frames=None, gpu_unique: bool = False,
-                 gpu_reindex: bool = False):
+                 gpu_reindex: bool = False, gpu_global_tiling: bool = False):
         F, Q = v.frames, v.tiles_per_frame
         vsize = int(np.asarray(v.palettes).shape[-1])  # the palette size is the palettes' last dimension
         if palsize is not None and int(palsize) != vsize:
@@ -72,6 +73,8 @@ class Encoder:
         # UseCount, ReindexTiles and every TileMap remap on the GPU (tiler_tile_use_count, tiler_reindex_tiles,
         # tiler_gather_tiles, tiler_remap_items); the arrays stay numpy, as with gpu_unique
         self.gpu_reindex = bool(gpu_reindex)
+        # DoGlobalTiling's plan, K-Modes, medoids and merges in one library call (tiler_global_tiling)
+        self.gpu_global_tiling = bool(gpu_global_tiling)
         self.n_frames = F
         self.kf_start = np.asarray(v.kf_start, np.int64)
         own = np.arange(F) if frames is None else np.asarray(frames, np.int64)
@@ -178,8 +181,9 @@ class Encoder:
     def do_global_tiling(self, desired: int, restart: int = gt.CRANDOM_KMODES_COUNT):
         """DoGlobalTiling main.pas:4256-4370: K-Modes merge per palette bin (GPU, all bins batched),
         FinishMergeTiles, MakeTilesUnique over all tiles, ReindexTiles."""
-        pp, act, uc, mi, kpb = gt.do_global_tiling(self.palpix, self.dith_pal, self.n_palettes, desired,
-                                                   self.palsize, restart, self.active, self.use_count)
+        step = gt.do_global_tiling_gpu if self.gpu_global_tiling else gt.do_global_tiling
+        pp, act, uc, mi, kpb = step(self.palpix, self.dith_pal, self.n_palettes, desired, self.palsize, restart,
+                                    self.active, self.use_count)
         self.palpix, self.active, self.use_count = pp, act, uc
         self.finish_merge_tiles(mi)
         self.make_tiles_unique()

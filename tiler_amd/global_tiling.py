@@ -6,6 +6,9 @@ reference runs the bins concurrently with ProcThreadPool, main.pas:4339):
   write_tile_dataset_line  WriteTileDatasetLine main.pas:4167-4183 (+ GetTilePalZoneThres 4142-4165)
   equal_quality_tile_count EqualQualityTileCount main.pas:722-725
   do_global_tiling         DoGlobalTiling 4256-4331 + DoKModes 4195-4254 + MergeTiles 3688-3712
+  do_global_tiling_gpu     the same through one library call (tiler_global_tiling): the plan and the merges on the GPU too
+  tile_dataset_lines_gpu / global_tiling_counts
+                           its dataset-line kernel and its cluster counts alone
   make_tiles_unique        MakeTilesUnique 2555-2612 (stable order: lowest index represents duplicates)
   make_tiles_unique_gpu    the same on the GPU (tiler_make_tiles_unique), any number of chunks in one call
   reindex_tiles            ReindexTiles 4483-4527 (UseCount desc, old index asc)
@@ -179,6 +182,73 @@ def do_global_tiling(palpix, dith_pal, n_palettes: int, desired: int, palsize: i
     res = kmodes_bins(plan, plan.run, palsize)
     pp, act, uc, mi = apply_kmodes_merges(plan, res, palpix, active, use_count)
     return pp, act, uc, mi, plan.k_per_bin
+
+
+# ---- the K-Modes branch on the GPU (tiler_amd/csrc/global_tiling.hip): numpy arrays in and out ----
+def global_tiling_counts(bin_size, desired: int):
+    """plan_global_tiling's cluster counts alone (tiler_global_tiling_counts, host code): bin_size [n_palettes] ->
+    (k int64 [n_palettes] = k_per_bin, run bool [n_palettes])."""
+    b = np.asarray(bin_size)
+    if b.ndim != 1 or b.size < 1:
+        raise ValueError("global_tiling_counts: bin_size must be [n_palettes], n_palettes >= 1")
+    if b.dtype.kind not in "iu":
+        raise ValueError("global_tiling_counts: bin_size must hold integers")
+    if int(b.min()) < 0 or int(b.max()) >= (1 << 31):
+        raise ValueError("global_tiling_counts: a bin size outside [0, 2^31)")
+    b = np.ascontiguousarray(b, np.int32)
+    k = np.zeros(b.size, np.int32)
+    run = np.zeros(b.size, np.uint8)
+    check(load().tiler_global_tiling_counts(_vp(b), b.size, int(desired), _vp(k), _vp(run)),
+          "tiler_global_tiling_counts")
+    return k.astype(np.int64), run.astype(bool)
+
+
+def tile_dataset_lines_gpu(tiles, palsize: int = 16, lines: bool = True, signi: bool = True):
+    """write_tile_dataset_line and pal_signi on the GPU (tiler_tile_dataset_lines): (lines [T][80] u8, pal_signi [T]
+    i32); an output switched off is None."""
+    t = np.asarray(tiles)
+    if t.dtype != np.uint8:
+        raise ValueError("tile_dataset_lines_gpu: tiles must be uint8")
+    if t.size % 64 or (t.ndim != 1 and t.shape[-1] != 64 and t.shape[-2:] != (8, 8)):
+        raise ValueError("tile_dataset_lines_gpu: tiles must be [T][64]")
+    t = np.ascontiguousarray(t).reshape(-1, 64)
+    T = t.shape[0]
+    out_l = np.zeros((T, 80), np.uint8) if lines else None
+    out_s = np.zeros(T, np.int32) if signi else None
+    check(load().tiler_tile_dataset_lines(_vp(t), T, int(palsize), _vp(out_l), _vp(out_s)),
+          "tiler_tile_dataset_lines")
+    return out_l, out_s
+
+
+def do_global_tiling_gpu(palpix, dith_pal, n_palettes: int, desired: int, palsize: int = 16,
+                         restart: int = CRANDOM_KMODES_COUNT, active=None, use_count=None, return_plan: bool = False):
+    """do_global_tiling with the plan, the K-Modes batch, the medoids and the merges in one library call
+    (tiler_global_tiling): the same (palpix, active, use_count, merge_index, k_per_bin).  return_plan: a sixth
+    element {"bin_size", "k", "start"} (int32 [n_palettes] each: plan_global_tiling's bin sizes, k_per_bin and
+    starts)."""
+    pp = np.array(palpix, np.uint8, copy=True, order="C").reshape(-1, 64)
+    T = pp.shape[0]
+    act = np.ones(T, np.uint8) if active is None else np.array(active, np.uint8, copy=True, order="C")
+    uc = np.ones(T, np.int64) if use_count is None else np.array(use_count, np.int64, copy=True, order="C")
+    dp = np.asarray(dith_pal)
+    if dp.dtype.kind not in "iu":
+        raise ValueError("do_global_tiling_gpu: dith_pal must hold integers")
+    if act.shape != (T,) or uc.shape != (T,) or dp.shape != (T,):
+        raise ValueError("do_global_tiling_gpu: dith_pal, active and use_count must be [T]")
+    if dp.dtype != np.int32 and T and (int(dp.min()) < -(1 << 31) or int(dp.max()) >= (1 << 31)):
+        raise ValueError("do_global_tiling_gpu: a dith_pal value does not fit 32 bits")
+    dp = np.ascontiguousarray(dp, np.int32)
+    n_palettes = int(n_palettes)
+    if n_palettes < 1:
+        raise ValueError("do_global_tiling_gpu: n_palettes must be at least 1")
+    mi = np.full(T, -1, np.int64)
+    size = np.zeros(n_palettes, np.int32)
+    k = np.zeros(n_palettes, np.int32)
+    start = np.zeros(n_palettes, np.int32) if return_plan else None
+    check(load().tiler_global_tiling(_vp(pp), _vp(dp), _vp(act), _vp(uc), _vp(mi), T, n_palettes, int(palsize),
+                                     int(desired), int(restart), _vp(size), _vp(k), _vp(start)), "tiler_global_tiling")
+    out = (pp, act, uc, mi, k.astype(np.int64))
+    return out + ({"bin_size": size, "k": k, "start": start},) if return_plan else out
 
 
 def make_tiles_unique(palpix, active, use_count):

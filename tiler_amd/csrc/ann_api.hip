@@ -1175,14 +1175,11 @@ int ann_kdtree_get_stats(ann_kdtree *t, tiler_search_stats *out) {
     if (const NNIndex *ix = t->ix; ix->last.flat_dev) {  // queries in all-flat shortlist workgroups
         int others = 0;
         TILER_HIP_CHECK(hipMemcpy(&others, ix->last.flat_dev, sizeof(int), hipMemcpyDeviceToHost));
-        const long wf0 = std::min(ix->last.flat_wgs, (others + ix->last.flat_qpw - 1) / ix->last.flat_qpw);
-        out->searched_flat_queries = wf0 < ix->last.flat_wgs ? ix->last.flat_nq - wf0 * ix->last.flat_qpw : 0;
+        out->searched_flat_queries = flat_queries(ix->last.flat, others);
         out->flat_queries = out->searched_flat_queries;
-        if (ix->last.ft_nonflat >= 0) {  // distinct tiles searched: the same layout over the call's own tiles
-            const long qpw = ix->last.flat_qpw, Q = (long)ix->last.queries;
-            const long wgs = (Q + qpw - 1) / qpw, w0 = std::min(wgs, ((long)ix->last.ft_nonflat + qpw - 1) / qpw);
-            out->flat_queries = w0 < wgs ? Q - w0 * qpw : 0;
-        }
+        if (ix->last.ft_nonflat >= 0)  // distinct tiles searched: the same layout over the call's own tiles
+            out->flat_queries = flat_queries(flat_layout((long)ix->last.queries, ix->last.flat.queries_per_wg),
+                                             (long)ix->last.ft_nonflat);
     }
     if (t->ix->kd && t->ix->scratch.kd_count) {
         int c = 0;

@@ -634,6 +634,8 @@ __global__ __launch_bounds__(NW * 64, 1) void nn_shortlist16_kernel(const half8 
                                                                 float *__restrict__ out_key,
                                                                 int *__restrict__ out_idx, const int *flat_cnt,
                                                                 const float2 *__restrict__ gate, float gb) {
+    // all-flat from workgroup first_flat_wg(*flat_cnt, NW * QB * 16) on (search_plan.hpp), as the stats count them;
+    // written without the division: calling it here compiles to other code
     if (flat_cnt && (long)blockIdx.x * (NW * QB * 16) >= (long)*flat_cnt)
         shortlist16_body<S, L, CB, NW, QB, true>(cfrag, cseed, nblk, qfrag, nq, blk_per_split, nsplit, perm, out_key,
                                                  out_idx, gate, gb);
@@ -1052,8 +1054,8 @@ __global__ __launch_bounds__(256) void nn_exact_kernel(RescoreArgs a, int list_n
 // sum), the K best per (thread, query) by (distance, tie order); then the workgroup's K best per query -> partials
 // [q][split][K].  nn_scan_merge_kernel picks the k best of each query's partials.  No MFMA, no tiers: the shortlist's
 // fixed costs (a 512-query workgroup per split, fragment prep, rescore) dominated a call of one query (0.6 ms).
+// (SCAN_D_MAX and the scan's plan: search_plan.hpp)
 // ------------------------------------------------------------------------------------------
-static constexpr int SCAN_D_MAX = 256;
 // One term of the reference's sequential sum, d + (q - c)^2 rounded after the product and after the sum (the mode's
 // IEEE single ops, as the compiler's own).  Written as one asm block so that the vectoriser cannot pack the
 // independent per-query sums into v_pk_add_f32 / v_pk_mul_f32 with v_mov shuffles (measured slower here).
@@ -1573,7 +1575,7 @@ NNIndex *nn_index_create_dev(float *d_rows, int n, int d, int bs, int split, hip
     return ix;
 }
 
-static constexpr int TIER2_MAX = 65536;  // generic tier 2: queries per collect chunk (every tier-2 query has a slot)
+// (TIER2_MAX, generic tier 2's queries per collect chunk: search_plan.hpp)
 static constexpr int TIER2_CAP = 1024;   // generic tier 2: collected candidates per query (beyond: tier 3)
 
 // The scratch's three buffer groups, each sized in one place (0: released; idle: the caller has waited for the device).
@@ -1649,16 +1651,7 @@ static int ensure_scratch(NNIndex *ix, long nq, long nkeys) {
 
 int nn_ensure_rootbox(NNIndex *ix, int nq) { return ensure_scratch(ix, nq, 0); }
 
-// waves per workgroup of the 32x32x16 shortlist on 64-d rows (UseOne's k = 8 preselection, main.pas:3830): two query
-// blocks of 32 per wave, so 64 * NW queries per workgroup
-static constexpr int GEN_NW_S4 = 4;
-static constexpr int GEN_QB_S4 = 1;  // query blocks per wave there: 16,384 items x 4 splits fill 2 waves per SIMD
-#ifndef GEN_QB_S4_BIG
-#define GEN_QB_S4_BIG 2  // ... and from 32,768 items (whole-tileset keyframes: ~64k) two, each A fragment feeding 2 MFMAs
-                         // (r06qb, profiles/r06/qb_preselect_qb2_encoder_ab.txt: whole-tileset loop 9.51 -> 9.59 Mtiles/s)
-#endif
-static int gen_qb_s4(int nq) { return nq >= 32768 ? GEN_QB_S4_BIG : GEN_QB_S4; }
-
+// The shortlists' shapes (GEN_*, SL16_*) and launch plans (generic_plan) are in search_plan.hpp.
 template <int S, int L, int CB, int NW, int QB = 2>
 static void launch_shortlist(NNIndex *ix, int nq, int nsplit, int bps, hipStream_t stream) {
     const int nqblk = (nq + 31) / 32;
@@ -1670,18 +1663,14 @@ static void launch_shortlist(NNIndex *ix, int nq, int nsplit, int bps, hipStream
                        ix->scratch.key, ix->scratch.idx);
 }
 
-// 16x16x32 shortlist (nn_shortlist16_kernel) for D = 161..192 float datasets without mirror orbits: SL16_L list
-// entries per lane; QB = 4 query blocks per wave; 5 (252 VGPRs) measured the same at 388k candidates (r03h: 80.6-81.2
-// vs 80.9-81.1 ms)
-static constexpr int SL16_NW = 8, SL16_QB = 4, SL16_CB = 8, SL16_L = 4;
 static std::atomic<int> g_gate16{1};  // tiler_debug_shortlist_gate: the k = 1 insertion gate (A/B timing hook)
 bool nn_generic_takes_flat(const NNIndex *ix) { return ix->S16 > 0; }
 
+// the 16x16x32 shortlist (nn_shortlist16_kernel) over the plan's workgroups and splits
 template <int S, int L>
-static int launch_shortlist16(NNIndex *ix, int nq, int nsplit, int bps, bool gated, const int *flat_cnt,
+static int launch_shortlist16(NNIndex *ix, int nq, const GenericPlan &p, bool gated, const int *flat_cnt,
                               hipStream_t stream) {
-    const int nqblk = (nq + 15) / 16;
-    const dim3 grid((nqblk + SL16_NW * SL16_QB - 1) / (SL16_NW * SL16_QB), nsplit);
+    const dim3 grid(p.wgs, p.nsplit);
     const size_t buf = SL16_CB * S * 1024 + SL16_CB * 64;
     float gb = 0.0f;
     if (gated) {  // the k = 1 gate (gate16_kernel): per query (x, y) from the query statistics, gb = (1 + g)/(1 - g)
@@ -1695,15 +1684,13 @@ static int launch_shortlist16(NNIndex *ix, int nq, int nsplit, int bps, bool gat
     }
     KTimer tm("nn_shortlist", stream);
     hipLaunchKernelGGL((nn_shortlist16_kernel<S, L, SL16_CB, SL16_NW, SL16_QB>), grid, dim3(SL16_NW * 64), 2 * buf, stream,
-                       (const half8 *)ix->d_frag16, ix->d_seed16, ix->nblk16, (const half8 *)ix->scratch.qfrag16, nq, bps,
-                       nsplit, ix->perm, ix->scratch.key, ix->scratch.idx, flat_cnt,
+                       (const half8 *)ix->d_frag16, ix->d_seed16, ix->nblk16, (const half8 *)ix->scratch.qfrag16, nq, p.bps,
+                       p.nsplit, ix->perm, ix->scratch.key, ix->scratch.idx, flat_cnt,
                        gated ? (const float2 *)ix->scratch.gate : nullptr, gb);
     TILER_HIP_CHECK(hipGetLastError());
     if (flat_cnt) {  // flat_queries of the stats: derived from the device count when they are read
         ix->last.flat_dev = flat_cnt;
-        ix->last.flat_nq = nq;
-        ix->last.flat_qpw = SL16_NW * SL16_QB * 16;
-        ix->last.flat_wgs = grid.x;
+        ix->last.flat = FlatLayout{nq, p.qpwg, p.wgs};
     }
     return 0;
 }
@@ -1776,19 +1763,12 @@ static int launch_exact(RescoreArgs ra, int list_n, int grid, hipStream_t stream
 
 static int search_tail(NNIndex *ix, const RescoreArgs &ra, int nq, hipStream_t stream, const OrbitTail *orbit);
 
-// generic tier-2 slots of a search: whole chunks covering 1.5x the largest tier-2 count of the recent searches (this
-// index's last count, or the last one seen on any index: an encoder builds a new index per keyframe), >= 1 chunk.
-// A fresh index (the 1 << 30 sentinel: no search of its own yet) takes 3x the recent count of the other indexes, a
-// margin for an unrelated one.  Queries past the slots go to the exhaustive tier 3: exact either way, slower.
+// generic tier-2 slots of a search (tier2_slots, search_plan.hpp) from this index's last tier-2 count and the last
+// one seen on any index
 static std::atomic<int> g_t2_recent{0};
 static int tier2_slots(NNIndex *ix, int nq) {
     const int own = ix->h_fb_count ? ((volatile int *)ix->h_fb_count)[0] : 0;
-    const bool fresh = own >= (1 << 30);
-    const int recent = g_t2_recent.load(std::memory_order_relaxed);
-    const int prev = fresh ? 2 * recent : std::max(own, recent);
-    const long want = (long)prev + prev / 2 + 1;
-    const long chunks = std::max(1L, (want + TIER2_MAX - 1) / TIER2_MAX);
-    return (int)std::min<long>(nq, chunks * TIER2_MAX);
+    return tier2_slots(own, g_t2_recent.load(std::memory_order_relaxed), nq);
 }
 static int search_core(NNIndex *ix, RescoreArgs &ra, const float *d_q, int nq, int k, hipStream_t stream,
                        const SearchOpts &opt);
@@ -1868,11 +1848,8 @@ int nn_search_dev(NNIndex *ix, const float *d_q, int nq, int k, int *d_idx, floa
     return 0;
 }
 
-// the small-batch path (nn_scan_small_kernel): groups of up to 16 queries (k = 1) or 4 (k <= 8) per workgroup row,
-// batches of up to SCAN_MAX1 / SCAN_MAX8 queries
-static constexpr int SCAN_QN1 = 16, SCAN_QN8 = 4;
-static constexpr long SCAN_ROWS_MAXN = 65536;   // nn_scan_rows_kernel up to this many candidates
-static constexpr long SCAN_ORB_MAXBLK = 1024;  // the orbit scan's splits (64-group blocks) at most: the wide merge's
+// the small-batch path (nn_scan_small_kernel): batches of up to g_scan_max1 (k = 1) / g_scan_max8 (k <= 8) queries;
+// which scan, its splits and its kernel instance: scan_plan (search_plan.hpp)
 static std::atomic<int> g_scan_max1{64}, g_scan_max8{16};  // tiler_set_scan_limits
 void nn_set_scan_limits(int max_k1, int max_k8) {
     g_scan_max1.store(std::max(0, max_k1));
@@ -1882,21 +1859,20 @@ void nn_set_force_replay(int on) { g_force_replay.store(on != 0); }
 void nn_set_shortlist_gate(int on) { g_gate16.store(on != 0); }
 bool nn_search_is_small(const NNIndex *ix, int nq, int k) { return scan_small_takes(ix, nq, k); }
 static bool scan_small_takes(const NNIndex *ix, int nq, int k) {
-    return ix->d <= SCAN_D_MAX && ix->d % 4 == 0 &&
-           ((k == 1 && nq <= g_scan_max1.load(std::memory_order_relaxed)) ||
-            (k <= 8 && nq <= g_scan_max8.load(std::memory_order_relaxed)));
+    return scan_takes(ix->d, nq, k, g_scan_max1.load(std::memory_order_relaxed),
+                      g_scan_max8.load(std::memory_order_relaxed));
 }
 static int scan_small(NNIndex *ix, RescoreArgs &ra, int nq, int k, hipStream_t stream) {
     const OrbitIndex *o = ix->orbit;
-    // mirror orbits: base rows only (nn_scan_orbit_kernel), one wave per (64-group block, query)
-    const long nblk = o ? ((long)o->G + 63) / 64 : 0;
-    const bool orb = o && o->d_base && o->G > 0 && ix->d == 192 && nblk <= SCAN_ORB_MAXBLK;
-    const int K = k == 1 ? 1 : 8;
-    // k = 1 on a plain index: the row-interleaved scan (nn_scan_rows_kernel); its copy is made on first use and waited
-    // for (a concurrent slot's scan may be queued on another stream as soon as this call releases the index)
-    // (at larger n the split-per-thread scan reads each row once for the batch's queries at near HBM peak: r05w2, the
-    // shuffled 262,144-row handle, 1 query 73 vs 77 us, batches slower)
-    const bool rows_scan = !orb && K == 1 && ix->d % 64 == 0 && ix->n <= SCAN_ROWS_MAXN;
+    const ScanPlan p = scan_plan(ix->n, ix->d, o && o->d_base ? (long)o->G : 0, nq, k);
+    if (p.kind == ScanKind::refused) {
+        set_error("scan_small: " + std::to_string(p.nsplit) + " candidate splits exceed the merge's 1024");
+        return -1;
+    }
+    const bool orb = p.kind == ScanKind::orbit, rows_scan = p.kind == ScanKind::rows;
+    const int nsplit = p.nsplit, qn = p.qn, K = p.K;
+    // the row-interleaved copy is made on first use and waited for (a concurrent slot's scan may be queued on another
+    // stream as soon as this call releases the index)
     if (rows_scan && !ix->d_rowsT) {
         const long nb = ((long)ix->n + 63) / 64;
         TILER_HIP_CHECK(dmalloc((void **)&ix->d_rowsT, (size_t)nb * 64 * ix->d * sizeof(float)));
@@ -1905,20 +1881,12 @@ static int scan_small(NNIndex *ix, RescoreArgs &ra, int nq, int k, hipStream_t s
         TILER_HIP_CHECK(hipGetLastError());
         TILER_HIP_CHECK(hipStreamSynchronize(stream));
     }
-    const int nsplit = orb ? (int)nblk
-                           : rows_scan ? (int)std::max<long>(1, ((long)ix->n + 63) / 64)
-                                       : (int)std::max<long>(1, std::min<long>(1024, ((long)ix->n + 255) / 256));
-    if (nsplit > 1024) {  // the merge holds one split per thread of one workgroup (the caps above keep this)
-        set_error("scan_small: " + std::to_string(nsplit) + " candidate splits exceed the merge's 1024");
-        return -1;
-    }
     if (ensure_scratch(ix, nq, (long)nq * nsplit * K)) return -1;
     SearchScratch &s = ix->scratch;
     ix->last.splits = 0;  // the stats report no tier-2 / tier-3 queries for a scan (fb_count is not read)
     ix->last.fallback = 0;
     KTimer tm("nn_scan", stream);
-    // the per-query work is unrolled over QN: the smallest instance that holds a group
-    const int qn = K == 1 ? (nq == 1 ? 1 : nq <= 4 ? 4 : SCAN_QN1) : (nq == 1 ? 1 : SCAN_QN8);
+    // the per-query work is unrolled over QN: the plan's qn is the smallest instance that holds a group
     const dim3 grid(nsplit, (nq + qn - 1) / qn);
     auto scan = [&](auto kern) {
         hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, ra, nsplit, s.key, s.idx);
@@ -1966,21 +1934,10 @@ static int search_core(NNIndex *ix, RescoreArgs &ra, const float *d_q, int nq, i
         ra.tq.ex_list = nullptr;
         return launch_exact(ra, nq, std::min(nq, 4096), stream);
     }
-    // 32x32x16 shortlist: 2 lanes x L = 8 per query (>= 2x the 4-way mirror near-ties of one tile per
-    // lane, row_perm spreads them 2+2); 16x16x32: 4 lanes x L16 (perm16 spreads them 1 per lane)
-    const int v16 = ix->S16 > 0 ? SL16_L : 0;
-    const int L = v16 ? v16 : 8;
-    const int lpq = v16 ? 4 : 2;
-    const int nblk = v16 ? ix->nblk16 : ix->nblk;
-    const int max_split = 64 / (lpq * L);
-    const int qpwg = v16 ? SL16_NW * SL16_QB * 16 : (ix->S == 12 ? 512 : ix->S == 4 ? 32 * gen_qb_s4(nq) * GEN_NW_S4 : 256);
-    const int wgs = (nq + qpwg - 1) / qpwg;
-    int nsplit = std::max(1, std::min(max_split, (1024 + wgs - 1) / wgs));
-    nsplit = std::min(nsplit, nblk);
-    const int bps = (nblk + nsplit - 1) / nsplit;
-    nsplit = (nblk + bps - 1) / bps;
-    ix->last.splits = nsplit;
-    if (ensure_scratch(ix, nq, (long)nq * nsplit * lpq * L)) return -1;
+    const GenericPlan p = generic_plan(ix->S, ix->S16, ix->nblk, ix->nblk16, nq);
+    const bool v16 = ix->S16 > 0;
+    ix->last.splits = p.nsplit;
+    if (ensure_scratch(ix, nq, (long)nq * p.nsplit * p.lpq * p.L)) return -1;
     SearchScratch &s = ix->scratch;
     TILER_HIP_CHECK(hipMemsetAsync(s.fb_count, 0, 16, stream));
     ix->last_orbit = 0;
@@ -2013,18 +1970,18 @@ static int search_core(NNIndex *ix, RescoreArgs &ra, const float *d_q, int nq, i
         }
         TILER_HIP_CHECK(hipGetLastError());
         {
-            if (launch_shortlist16<6, SL16_L>(ix, nq, nsplit, bps, k == 1 && g_gate16.load(std::memory_order_relaxed),
+            if (launch_shortlist16<6, SL16_L>(ix, nq, p, k == 1 && g_gate16.load(std::memory_order_relaxed),
                                          opt.flat_cnt, stream))
                 return -1;
         }
-    } else if (dispatch_shortlist<8>(ix, nq, nsplit, bps, stream)) {
+    } else if (dispatch_shortlist<8>(ix, nq, p.nsplit, p.bps, stream)) {
         return -1;
     }
     ra.key = s.key;
     ra.idx = s.idx;
-    ra.L = L;
-    ra.lpq = lpq;
-    ra.nsplit = nsplit;
+    ra.L = p.L;
+    ra.lpq = p.lpq;
+    ra.nsplit = p.nsplit;
     if (!s.ccnt) TILER_HIP_CHECK(scratch_size_collect(s, true));
     ra.ccnt = s.ccnt;
     ra.cbuf = s.cbuf;

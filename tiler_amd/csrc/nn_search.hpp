@@ -5,6 +5,7 @@
 
 #include "frame_tiling.hpp"
 #include "kdtree.hpp"
+#include "search_plan.hpp"
 #include "tiler_common.hpp"
 
 namespace tiler {
@@ -64,10 +65,10 @@ struct TierQueues {
 struct LastSearch {
     long long queries = 0, fallback = 0;
     int splits = 0;
-    // flat_queries: queries in all-flat shortlist workgroups, computed when the stats are read from the device count
-    // (flat_dev) and the launch shape; 0 when the search had no flat grouping
+    // flat_queries: queries in all-flat shortlist workgroups, computed when the stats are read (flat_queries,
+    // search_plan.hpp) from the device count (flat_dev) and the launch shape; 0 when the search had no flat grouping
     const int *flat_dev = nullptr;
-    long flat_nq = 0, flat_qpw = 0, flat_wgs = 0;
+    FlatLayout flat;
     // a FrameTiling call that searched its distinct tiles only (nn_frame_tiling_dev): queries is the call's Q, searched
     // the representatives, dup = Q - searched, ft_nonflat the call's non-flat tiles (duplicates included; -1: no such
     // call) from which flat_queries is reported in the call's own units

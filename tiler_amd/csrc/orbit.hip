@@ -557,7 +557,7 @@ __global__ __launch_bounds__(NW * 64, 1) void nn_orbit_shortlist_pipe_kernel(con
     // flat_cnt (or null: none) is the device count of the launch's non-flat queries, which come first: the workgroups
     // past them hold flat query tiles only (q' block 0) and run every candidate block block-serially with k-steps
     // 0..2, only those streamed
-    const int flat_wg0 = flat_cnt ? (max(0, *flat_cnt) + NW * QB * 32 - 1) / (NW * QB * 32) : 0x7fffffff;
+    const int flat_wg0 = flat_cnt ? first_flat_wg(max(0, *flat_cnt), NW * QB * 32) : 0x7fffffff;
     const bool flat = (int)blockIdx.x >= flat_wg0;
     const int nks = flat ? 3 : OS;
     if (flat) {
@@ -2014,8 +2014,6 @@ int orbit_build(NNIndex *ix, hipStream_t stream) {
     return 0;
 }
 
-static constexpr int ORB_L = 4, ORB_CB = 4, ORB_NW = 8, ORB_QB = 2;
-
 int orbit_ensure_queries(OrbitIndex *o, int nq) {
     if ((size_t)nq <= o->cap_q) return 0;
     const long nqblk = (nq + 31) / 32;
@@ -2032,56 +2030,19 @@ int orbit_search(NNIndex *ix, const float *d_q, int nq, const OrbitTail &tail, h
                  bool queries_prepared) {
     OrbitIndex *o = ix->orbit;
     const int nqblk = (nq + 31) / 32;
-    const int qpw = ORB_NW * ORB_QB;  // query blocks per workgroup (ORB_QB per wave)
-    const int wgs = (nqblk + qpw - 1) / qpw;
-    const int max_split = 32 / (2 * ORB_L);  // rescore: one list entry per lane of a half-wave
-    // One 8-wave workgroup fills a CU (2 waves per SIMD), so a launch runs in rounds of n_cu workgroups of
-    // ceil(gblk / ns) tile blocks each for ns candidate splits: pick the cheapest, preferring fewer splits (each adds
-    // list entries to rescore) unless more are >= 2 % faster.  C3: 1,519 workgroups, 1 split (5.93 -> 6 rounds);
-    // C2: 675 workgroups, 1 split (3 rounds of 512 blocks: 2.22 ms; 3 splits, 8 rounds of 171: 2.36 ms).
+    // the launch plan (search_plan.hpp); the CU count is read once
     static const int n_cu = [] {
         int dev = 0, cu = 256;
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev);
         return cu > 0 ? cu : 256;
     }();
-    // A workgroup also pays a fixed cost of about ORB_WG_FIXED tile blocks (prologue, list start-up, epilogue: C2
-    // with 3 splits ran 1.72 us per block-round against 1.26 at C3), so a round is priced as its blocks + that.
-    constexpr double ORB_WG_FIXED = 64.0;
-    int nsplit = 1;
-    double best_t = 1e30;
-    for (int ns = 1; ns <= max_split && ns <= o->gblk; ns++) {
-        const double t = std::ceil((double)wgs * ns / n_cu) * (std::ceil((double)o->gblk / ns) + ORB_WG_FIXED);
-        if (t < best_t * 0.98) {
-            best_t = t;
-            nsplit = ns;
-        }
-    }
-    // Mixed: when the last round of whole-candidate workgroups is ragged (C2: 675 workgroups = 2.64 rounds), the
-    // first R * n_cu workgroups scan every block and only the remaining ones split their blocks mix_ns ways
-    // (C2: 3 rounds of 576 -> 2 x 576 + 2 x 235 block-times).  Lists keep the mix_ns stride for every query;
-    // the whole-candidate part's other splits are empty entries.
-    int mix_full = 0;
-    {
-        const int R = wgs / n_cu, rem = wgs - R * n_cu;
-        for (int ns = 2; R >= 1 && rem > 0 && ns <= max_split && ns <= o->gblk; ns++) {
-            const double t = R * (o->gblk + ORB_WG_FIXED) +
-                             std::ceil((double)rem * ns / n_cu) * (std::ceil((double)o->gblk / ns) + ORB_WG_FIXED);
-            if (t < best_t * 0.98) {
-                best_t = t;
-                nsplit = ns;
-                mix_full = R * n_cu;
-            }
-        }
-    }
     // Flat query tiles (from *tail.flat_cnt on, FrameTiling moves them last): their q' has only block 0, so the
     // workgroups made of them alone run the block-serial body with 3 of the 12 k-steps on every candidate block
     // (d_1..d_3 are +-0 for them: the same bounds bit for bit).  The count stays on the device: the kernel derives its
     // first all-flat workgroup from it, with any candidate split (the mixed launch is not used then).
-    const int qpw_q = qpw * 32;  // queries per workgroup
     const int *flat_cnt = tail.flat_cnt;
-    if (flat_cnt) mix_full = 0;
-    const int bps = (o->gblk + nsplit - 1) / nsplit;
-    nsplit = (o->gblk + bps - 1) / bps;
+    const OrbitPlan p = orbit_plan(nq, o->gblk, n_cu, flat_cnt != nullptr);
+    const int wgs = p.wgs, nsplit = p.nsplit, bps = p.bps, mix_full = p.mix_full;
     if (orbit_ensure_queries(o, nq)) return -1;
     const size_t nkeys = (size_t)nq * nsplit * 2 * ORB_L;
     if (nkeys > o->cap_keys) {
@@ -2112,7 +2073,7 @@ int orbit_search(NNIndex *ix, const float *d_q, int nq, const OrbitTail &tail, h
         if (!mix_full) {
             shortlist(wgs, nsplit, 0, nq, bps, flat_cnt);
         } else {
-            const int qb_off = mix_full * qpw, q_off = qb_off * 32;  // query blocks / queries of part A
+            const int q_off = mix_full * p.queries_per_wg, qb_off = q_off / 32;  // queries / query blocks of part A
             const size_t na = (size_t)std::min(nq, q_off) * per_q;
             TILER_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)o->key, 0x7f800000u, na, stream));  // +inf: empty
             TILER_HIP_CHECK(hipMemsetAsync(o->id, 0xff, na * sizeof(int), stream));
@@ -2179,9 +2140,7 @@ int orbit_search(NNIndex *ix, const float *d_q, int nq, const OrbitTail &tail, h
     }
     ix->last.splits = nsplit;
     ix->last.flat_dev = flat_cnt;  // flat_queries: derived from the device count when the stats are read
-    ix->last.flat_nq = nq;
-    ix->last.flat_qpw = qpw_q;
-    ix->last.flat_wgs = wgs;
+    ix->last.flat = FlatLayout{nq, p.queries_per_wg, wgs};
     return 0;
 }
 
